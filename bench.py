@@ -14,6 +14,11 @@ One step (per rank):
 Metric: probe rows/s over the whole job (all ranks), max step time over ranks.
 
 Run: python bench.py [--gpus N] [--steps K] [--warmup W]
+                     [--dump-outputs DIR] [--full]
+A plain run sets up, warms up, times the K steps and prints one JSON line;
+--dump-outputs DIR also writes a canonical sample of the last timed step's
+join output as DIR/<name>.npy. --full is reserved for extra measurements
+beyond the headline figure (none today).
 Multi-GPU: torchrun --nproc-per-node N bench.py --gpus N (driver contract).
 """
 import argparse
@@ -138,16 +143,80 @@ def one_step_dry(build, chunks, world):
     return int(bset.item())
 
 
-def one_step(build_col, chunks, world, out_hint, comm_stream=None):
+DUMP_SEED = 20240611
+DUMP_MAX_PAIRS = 3 << 20        # x 2 float64 arrays = 48 MiB, under 64 MB
+
+
+class OutputSampler:
+    """Collects a fixed, seeded sample of the join output for --dump-outputs.
+
+    The probe kernel appends pairs in atomic-counter order, so positions in
+    the output differ from run to run; the set of pairs does not. The sample
+    is therefore taken by probe row: every pair whose global probe row index
+    is congruent to a seeded residue modulo a power-of-two stride, written
+    sorted by (probe row, build row). Per chunk it also keeps the exact pair
+    count and an order-independent checksum over ALL pairs (the int64 sum of
+    build row ^ low word of probe row, stored as two exact float64 halves).
+
+    inner_join returns only after reading back its match counter, so the GPU
+    is idle when the sampler is called; it synchronizes again before it
+    returns and accounts its own wall time in `seconds`, which the caller
+    takes out of the step time. The timed path itself runs unchanged."""
+
+    def __init__(self, probe_rows, chunk_rows):
+        target = 1 << 20
+        stride = 1
+        while probe_rows > stride * 2 * target:
+            stride *= 2
+        self.stride = stride
+        g = torch.Generator().manual_seed(DUMP_SEED)
+        self.residue = int(torch.randint(0, stride, (1,), generator=g))
+        self.chunk_rows = chunk_rows
+        self.parts = []
+        self.seconds = 0.0
+
+    def __call__(self, ci, bi, pi):
+        t0 = time.perf_counter()
+        off = ci * self.chunk_rows
+        r = (self.residue - off) % self.stride
+        lo = pi.view(torch.int32)[::2]      # low words: enough for both uses
+        sel = ((lo & (self.stride - 1)) == r).nonzero().squeeze(1)
+        chk = (bi ^ lo).sum(dtype=torch.int64)
+        self.parts.append((off, bi.numel(), chk, bi[sel], pi[sel]))
+        del lo, sel, chk
+        torch.cuda.synchronize()
+        self.seconds += time.perf_counter() - t0
+
+    def write(self, out_dir):
+        import numpy as np
+        os.makedirs(out_dir, exist_ok=True)
+        b = np.concatenate([p[3].cpu().numpy().astype(np.float64)
+                            for p in self.parts])
+        q = np.concatenate([(p[4].cpu().numpy() + p[0]).astype(np.float64)
+                            for p in self.parts])
+        order = np.lexsort((b, q))[:DUMP_MAX_PAIRS]
+        np.save(os.path.join(out_dir, "build_idx.npy"), b[order])
+        np.save(os.path.join(out_dir, "probe_idx.npy"), q[order])
+        np.save(os.path.join(out_dir, "num_pairs.npy"),
+                np.array([p[1] for p in self.parts], dtype=np.float64))
+        chk = [int(p[2]) for p in self.parts]
+        np.save(os.path.join(out_dir, "pair_checksum.npy"),
+                np.array([[c >> 32, c & 0xFFFFFFFF] for c in chk],
+                         dtype=np.float64))
+
+
+def one_step(build_col, chunks, world, out_hint, comm_stream=None, sink=None):
     from spark_rapids_jni_amd.columnar import Column
     from spark_rapids_jni_amd.ops.join import HashJoinTable
 
     # rebuild the table each step (config is build+probe)
     tbl = HashJoinTable.build(build_col)
     if world == 1:
-        for chunk in chunks:
+        for ci, chunk in enumerate(chunks):
             pcol = Column.from_torch(chunk)
             bi, pi = tbl.inner_join(pcol, out_hint=chunk.numel() + out_hint)
+            if sink is not None:
+                sink(ci, bi, pi)
             del pcol, bi, pi
         del tbl
         return
@@ -205,7 +274,22 @@ def main():
                     help="distinct groups for --op groupby")
     ap.add_argument("--codec", choices=["none", "snappy", "zstd", "gzip"],
                     default="none", help="parquet codec for --op parquet")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed "
+                         "step computed (a fixed, seeded, canonically "
+                         "ordered sample of the join gather maps, plus "
+                         "per-chunk pair counts and checksums) as "
+                         "DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run measurements beyond the headline figure "
+                         "(reserved: a plain run already does only setup, "
+                         "warmup and the timed steps)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and (args.op != "join" or args.dry_run
+                              or int(os.environ.get("WORLD_SIZE", "1")) > 1):
+        ap.error("--dump-outputs covers the single-GPU flagship join only")
 
     world, rank, local_rank = setup_dist(args)
     if args.op == "nds":
@@ -240,14 +324,15 @@ def main():
     # probe rows landing on this rank can exceed the chunk a bit at world>1
     out_hint = 0 if world == 1 else args.chunk_rows // 16
 
-    # pre-generate probe chunks (synthetic data stays fixed across steps;
-    # RNG cost is outside the timed region)
+    # pre-generate probe chunks (synthetic data stays fixed across steps and,
+    # being seeded, across runs; RNG cost is outside the timed region)
+    gen = torch.Generator(device=device).manual_seed(11 + rank)
     chunks = []
     done = 0
     while done < args.probe_rows:
         m = min(args.chunk_rows, args.probe_rows - done)
         chunks.append(torch.randint(0, key_space, (m,), dtype=torch.int64,
-                                    device=device))
+                                    device=device, generator=gen))
         done += m
 
     comm_stream = torch.cuda.Stream(device=device) if world > 1 else None
@@ -257,11 +342,20 @@ def main():
     barrier_sync(world)
 
     log(rank, f"[bench] timing {args.steps} steps")
+    sampler = (OutputSampler(args.probe_rows, args.chunk_rows)
+               if args.dump_outputs else None)
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        one_step(build_col, chunks, world, out_hint, comm_stream)
+    for i in range(args.steps):
+        # with --dump-outputs the last timed step hands each chunk's output
+        # to the sampler, whose own time is taken out again below
+        one_step(build_col, chunks, world, out_hint, comm_stream,
+                 sink=sampler if i == args.steps - 1 else None)
     barrier_sync(world)
     elapsed = time.perf_counter() - t0
+    if sampler is not None:
+        elapsed -= sampler.seconds
+        sampler.write(args.dump_outputs)
+        log(rank, f"[bench] wrote outputs to {args.dump_outputs}")
 
     # max over ranks
     if world > 1:

@@ -89,7 +89,9 @@ def build(verbose=False, asan_host=False):
 
     def batch(srcs, flags):
         outs = []
-        with ThreadPoolExecutor(max_workers=os.cpu_count()) as ex:
+        # MAX_JOBS (the torch extension convention) caps compile parallelism
+        njobs = int(os.environ.get("MAX_JOBS") or os.cpu_count() or 1)
+        with ThreadPoolExecutor(max_workers=max(1, njobs)) as ex:
             futs = [(s, ex.submit(_compile, s, flags, headers, cache, log))
                     for s, headers, flags in srcs]
             for s, f in futs:
