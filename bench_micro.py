@@ -37,6 +37,64 @@ def emit(name, rows, secs, bytes_processed=None):
     print(json.dumps(rec), flush=True)
 
 
+def ab_time(new_fn, old_fn, iters, repeats=5):
+    """Time two equivalent paths in the same process, alternating them, so a
+    drift of the machine's load hits both. Returns per-repeat seconds."""
+    new_s, old_s = [], []
+    for _ in range(repeats):
+        new_s.append(timeit(new_fn, iters))
+        old_s.append(timeit(old_fn, iters))
+    return new_s, old_s
+
+
+def emit_ab(name, rows, kept, new_s, old_s):
+    def stats(xs):
+        xs = sorted(xs)
+        return {"ms": round(xs[len(xs) // 2] * 1e3, 4),
+                "ms_min": round(xs[0] * 1e3, 4),
+                "ms_max": round(xs[-1] * 1e3, 4)}
+    for path, xs in (("hip", new_s), ("torch_parent", old_s)):
+        rec = {"bench": name, "path": path, "rows": rows, "kept": kept,
+               "repeats": len(xs)}
+        rec.update(stats(xs))
+        print(json.dumps(rec), flush=True)
+
+
+def compact_bench(n, iters, dev, g):
+    """Stream compaction and fused gather against the expressions they
+    replaced (torch.nonzero + one t[idx] per tensor), at 1/50/99 % kept."""
+    from spark_rapids_jni_amd.ops import compact
+    ri = lambda dt: torch.randint(-2**31, 2**31, (n,), device=dev,
+                                  generator=g).to(dt)
+    frame = [ri(torch.int64), ri(torch.int64), ri(torch.int64),
+             ri(torch.int32), ri(torch.int32),
+             torch.rand(n, dtype=torch.float64, device=dev, generator=g),
+             torch.rand(n, device=dev, generator=g) < 0.9,
+             torch.rand(n, device=dev, generator=g) < 0.9]
+    u = torch.rand(n, device=dev, generator=g)
+    for kept in (0.01, 0.5, 0.99):
+        m = u < kept
+
+        def parent_nonzero():
+            return torch.nonzero(m, as_tuple=False).view(-1)
+
+        def parent_frame():
+            idx = torch.nonzero(m, as_tuple=False).view(-1)
+            return [t[idx] for t in frame]
+
+        new_s, old_s = ab_time(lambda: compact.nonzero(m), parent_nonzero,
+                               iters)
+        emit_ab("compact_nonzero", n, kept, new_s, old_s)
+        new_s, old_s = ab_time(lambda: compact.compact_tensors(frame, m),
+                               parent_frame, iters)
+        emit_ab("compact_frame_8col", n, kept, new_s, old_s)
+    for kept in (0.01, 0.5, 0.99):
+        idx = torch.nonzero(u < kept, as_tuple=False).view(-1)
+        new_s, old_s = ab_time(lambda: compact.gather_tensors(frame, idx),
+                               lambda: [t[idx] for t in frame], iters)
+        emit_ab("gather_frame_8col", n, kept, new_s, old_s)
+
+
 def plumbing_bench():
     """BASELINE config[0]: murmur3 + row<->columnar on a 1k-row int64 batch
     via the HOST path (no GPU) — measures binding/plumbing overhead like the
@@ -179,6 +237,10 @@ def main():
     emit("parse_uri_host", uc.size, secs, int(uc.offsets[-1].item()))
     secs = timeit(lambda: parse_uri(uc, UriPart.QUERY_KEY, "k"), args.iters)
     emit("parse_uri_query_key", uc.size, secs)
+
+    # 7. stream compaction / fused multi-column gather vs the torch
+    #    expressions they replaced
+    compact_bench(n, args.iters, dev, g)
 
 
 if __name__ == "__main__":

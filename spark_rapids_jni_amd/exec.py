@@ -11,7 +11,7 @@ import torch
 
 from . import parquet as pq
 from .columnar import Column, DType, Table
-from .ops import hashing
+from .ops import compact, hashing
 from .ops.aggregate import Agg, groupby
 from .ops.copying import gather, gather_column
 from .ops.join import HashJoinTable
@@ -19,8 +19,10 @@ from .ops.join import HashJoinTable
 
 def apply_boolean_mask(table: Table, mask: torch.Tensor) -> Table:
     """Keep rows where mask != 0 (Spark Filter)."""
-    sel = torch.nonzero(mask, as_tuple=False).view(-1)
-    return gather(table, sel)
+    if isinstance(mask, torch.Tensor) and mask.dtype not in (
+            torch.bool, torch.uint8, torch.int8):
+        mask = mask != 0
+    return compact.apply_boolean_mask(table, mask)
 
 
 def scan_parquet(path: str, columns=None, device="cuda") -> Table:

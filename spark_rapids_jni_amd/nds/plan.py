@@ -115,34 +115,55 @@ class Frame:
         return list(self.cols.keys())
 
     def gather(self, idx: torch.Tensor, null_for_neg=False) -> "Frame":
+        if not null_for_neg:
+            from ..ops.compact import gather_tensors
+            return self._rebuild(
+                gather_tensors(self._tensors(), idx.long()), idx.numel())
+        # outer join: a negative entry makes a null row
         out = {}
         n = idx.numel()
-        if null_for_neg:
-            neg = idx < 0
-            safe = idx.clamp(min=0)
+        neg = idx < 0
+        safe = idx.clamp(min=0)
         for name, v in self.cols.items():
-            if null_for_neg:
-                if v.data.numel() == 0:
-                    # empty side of an outer join: all rows are null
-                    data = torch.zeros(n, dtype=v.data.dtype,
-                                       device=idx.device)
-                    out[name] = Val(data, torch.zeros(
-                        n, dtype=torch.bool, device=idx.device), v.dict)
-                    continue
-                data = v.data[safe]
-                valid = v.valid[safe] if v.valid is not None else \
-                    torch.ones(n, dtype=torch.bool, device=data.device)
-                valid = valid & ~neg
-                out[name] = Val(data, valid, v.dict)
-            else:
-                data = v.data[idx]
-                valid = v.valid[idx] if v.valid is not None else None
-                out[name] = Val(data, valid, v.dict)
+            if v.data.numel() == 0:
+                # empty side of an outer join: all rows are null
+                data = torch.zeros(n, dtype=v.data.dtype,
+                                   device=idx.device)
+                out[name] = Val(data, torch.zeros(
+                    n, dtype=torch.bool, device=idx.device), v.dict)
+                continue
+            data = v.data[safe]
+            valid = v.valid[safe] if v.valid is not None else \
+                torch.ones(n, dtype=torch.bool, device=data.device)
+            valid = valid & ~neg
+            out[name] = Val(data, valid, v.dict)
+        return Frame(out, n, self.sharded)
+
+    def _tensors(self):
+        """All data and non-None validity tensors, in column order."""
+        ts = []
+        for v in self.cols.values():
+            ts.append(v.data)
+            if v.valid is not None:
+                ts.append(v.valid)
+        return ts
+
+    def _rebuild(self, ts, n) -> "Frame":
+        """Inverse of _tensors(): a frame of n rows over the moved tensors."""
+        it = iter(ts)
+        out = {}
+        for name, v in self.cols.items():
+            data = next(it)
+            valid = next(it) if v.valid is not None else None
+            out[name] = Val(data, valid, v.dict)
         return Frame(out, n, self.sharded)
 
     def mask(self, m: torch.Tensor) -> "Frame":
-        idx = torch.nonzero(m, as_tuple=False).view(-1)
-        return self.gather(idx)
+        from ..ops.compact import compact_tensors
+        if m.dtype not in (torch.bool, torch.uint8, torch.int8):
+            m = m != 0
+        ts, k = compact_tensors(self._tensors(), m)
+        return self._rebuild(ts, k)
 
     def to_rows(self, decode=True):
         """Host list-of-tuples with None for nulls (tests/oracle compare)."""
@@ -243,8 +264,8 @@ class GpuBackend:
                 # hash table over the big input for a handful of probes
                 ltbl = HashJoinTable.build(pcols)
                 matched = ltbl.mark_matches(bcols).bool()
-                sel = torch.nonzero(matched if how == "semi" else ~matched,
-                                    as_tuple=False).view(-1)
+                from ..ops.compact import nonzero
+                sel = nonzero(matched if how == "semi" else ~matched)
                 return sel, None
             tbl = HashJoinTable.build(bcols)
             sel = tbl.semi_join(pcols, anti=(how == "anti"))
@@ -766,11 +787,12 @@ class Engine:
             keynames = keys + list(extra_keys.keys())
         # distinct (keys, value): drop null values first (countd skips nulls)
         if v.valid is not None:
-            keep = torch.nonzero(v.valid, as_tuple=False).view(-1)
-            kv = [Val(x.data[keep],
-                      x.valid[keep] if x.valid is not None else None,
-                      x.dict) for x in kv]
-            v = Val(v.data[keep], None, v.dict)
+            from ..ops.compact import compact_tensors
+            kf = Frame(dict(enumerate(kv + [v])), f.nrows)
+            kept, nkeep = compact_tensors(kf._tensors(), v.valid)
+            kept = list(kf._rebuild(kept, nkeep).cols.values())
+            kv = kept[:-1]
+            v = Val(kept[-1].data, None, v.dict)
         kvals, _r, ng = self.backend.groupby(kv + [v], [("count", None)])
         dist = Frame(self._kv_dict(keynames + ["__v"], kvals, []), ng,
                      sharded=f.sharded)
@@ -1109,8 +1131,7 @@ class Engine:
         h = self._key_hash(f, keys)
         part = h % self.world
         if not f.sharded:
-            keep = torch.nonzero(part == self.rank, as_tuple=False).view(-1)
-            g = f.gather(keep)
+            g = f.mask(part == self.rank)
             g.sharded = True
             return g
         return self._exchange(f, part)

@@ -31,6 +31,7 @@ PYBIND11_MODULE(_gpu, m) {
   register_hash(m);
   register_hashtable(m);
   register_copying(m);
+  register_compact(m);
   register_sort(m);
   register_rowconv(m);
   register_shuffle(m);
