@@ -95,6 +95,101 @@ def compact_bench(n, iters, dev, g):
         emit_ab("gather_frame_8col", n, kept, new_s, old_s)
 
 
+def parent_argsort(by, n, dev):
+    """The expression NDS Sort/Window used before the native sort order:
+    per key two gathers, a fill, a torch.argsort and a perm[o]. `by` is a
+    list of (data, valid, ascending), first key primary."""
+    perm = torch.arange(n, dtype=torch.int64, device=dev)
+    for data, valid, asc in reversed(by):
+        d = data[perm]
+        if d.dtype == torch.bool:
+            d = d.to(torch.int8)
+        if valid is not None:
+            vm = valid[perm]
+            if d.dtype.is_floating_point:
+                fill = float("-inf") if asc else float("inf")
+            else:
+                ii = torch.iinfo(d.dtype)
+                fill = ii.min if asc else ii.max
+            d = torch.where(vm, d, torch.full_like(d, fill))
+        o = torch.argsort(d, stable=True, descending=not asc)
+        perm = perm[o]
+    return perm
+
+
+def count_launches(fn):
+    """GPU kernels launched by one call of fn (None without a profiler)."""
+    try:
+        from torch.profiler import ProfilerActivity, profile
+        fn()
+        torch.cuda.synchronize()
+        with profile(activities=[ProfilerActivity.CUDA]) as prof:
+            fn()
+            torch.cuda.synchronize()
+        return sum(1 for e in prof.events()
+                   if str(e.device_type).endswith("CUDA"))
+    except Exception:  # the count is a report, not part of the timing
+        return None
+
+
+def sort_order_bench(n, iters, dev, g):
+    """sort_order_tensors against the expression it replaced in NDS
+    (parent_argsort) on four key sets. Median of `reps` timings."""
+    from spark_rapids_jni_amd.ops.sort import sort_order_tensors
+    ri = lambda lo, hi, dt: torch.randint(lo, hi, (n,), device=dev,
+                                          generator=g).to(dt)
+    valid = lambda: torch.rand(n, device=dev, generator=g) < 0.9
+    # the extremes stay out: the old expression ties them with its null fill
+    i32 = lambda: ri(-2**31 + 1, 2**31 - 1, torch.int32)
+    code = lambda: ri(0, 1000, torch.int64)
+    # (data, valid, ascending, key_bits)
+    sets = {
+        "int64_full": [(ri(-2**63, 2**63 - 1, torch.int64), None, True, None)],
+        "int32": [(i32(), None, True, None)],
+        "2x_int32_nullable": [(i32(), valid(), True, None),
+                              (i32(), valid(), False, None)],
+        "nds_6key": [(code(), None, True, 10), (code(), None, True, 10),
+                     (code(), None, False, 10), (i32(), None, True, None),
+                     (i32(), None, True, None),
+                     (torch.rand(n, dtype=torch.float64, device=dev,
+                                 generator=g), valid(), True, None)],
+    }
+    # what NDS Sort passes: the sort keys plus every other column of the
+    # frame as a tie-breaker
+    f64 = lambda: torch.rand(n, dtype=torch.float64, device=dev, generator=g)
+    sets["nds_12key"] = sets["nds_6key"] + [
+        (code(), None, True, 10), (code(), None, True, 10),
+        (code(), valid(), True, 10), (f64(), None, True, None),
+        (f64(), valid(), True, None), (i32(), valid(), True, None)]
+    reps = 20
+    inner = max(1, min(iters, 20)) if n <= 2**16 else 1
+    for name, ks in sets.items():
+        keys = [k[0] for k in ks]
+        valids = [k[1] for k in ks]
+        asc = [k[2] for k in ks]
+        bits = [k[3] for k in ks]
+        by = [(k[0], k[1], k[2]) for k in ks]
+        # nulls first in either direction, as parent_argsort's fill does
+        new = lambda: sort_order_tensors(keys, valids, asc, [True] * len(ks),
+                                         bits)
+        old = lambda: parent_argsort(by, n, dev)
+        assert torch.equal(new(), old()), name
+        new_s, old_s = ab_time(new, old, inner, repeats=reps)
+        launches = {"hip": count_launches(new),
+                    "torch_parent": count_launches(old)}
+
+        def stats(xs):
+            xs = sorted(xs)
+            return {"ms": round(xs[len(xs) // 2] * 1e3, 4),
+                    "ms_min": round(xs[0] * 1e3, 4),
+                    "ms_max": round(xs[-1] * 1e3, 4)}
+        for path, xs in (("hip", new_s), ("torch_parent", old_s)):
+            rec = {"bench": "sort_order_" + name, "path": path, "rows": n,
+                   "repeats": reps, "launches": launches[path]}
+            rec.update(stats(xs))
+            print(json.dumps(rec), flush=True)
+
+
 def plumbing_bench():
     """BASELINE config[0]: murmur3 + row<->columnar on a 1k-row int64 batch
     via the HOST path (no GPU) — measures binding/plumbing overhead like the
@@ -125,7 +220,15 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=2**24)
     ap.add_argument("--iters", type=int, default=5)
+    ap.add_argument("--only", choices=["sort_order"], default=None,
+                    help="run just this group")
     args = ap.parse_args()
+    if args.only == "sort_order":
+        g = torch.Generator(device="cuda")
+        g.manual_seed(7)
+        for sn in (256, 2048, 2**16, args.rows):
+            sort_order_bench(sn, 20, "cuda", g)
+        return
     plumbing_bench()  # CPU shape (BASELINE config[0]) first
     n = args.rows
     dev = "cuda"
@@ -241,6 +344,10 @@ def main():
     # 7. stream compaction / fused multi-column gather vs the torch
     #    expressions they replaced
     compact_bench(n, args.iters, dev, g)
+
+    # 8. multi-key sort order vs the per-key torch.argsort expression
+    for sn in (256, 2048, 2**16, n):
+        sort_order_bench(sn, args.iters, dev, g)
 
 
 if __name__ == "__main__":

@@ -469,6 +469,15 @@ class CpuBackend:
 # engine
 # ---------------------------------------------------------------------------
 
+# GPU sort routing, from the sort_order table in docs/PERF.md: the native
+# packed-key sort serves every frame of up to one tile (one launch per key
+# word) and every sort on more than two keys; on one or two keys above a
+# tile, torch's one-sweep radix sort measured faster by more than the spread
+# and the per-key expression is kept.
+NATIVE_SORT_ANY_KEYS_ROWS = 2048
+TORCH_SORT_MAX_KEYS = 2
+
+
 class Engine:
     def __init__(self, catalog, device="cuda", world: int = 1, rank: int = 0,
                  backend=None):
@@ -900,16 +909,20 @@ class Engine:
             inv[perm] = torch.arange(n, dtype=torch.int64, device=dev)
             # segment boundaries on partition keys (nulls group together:
             # a data difference only counts when both rows are valid)
-            bnd = torch.zeros(n, dtype=torch.bool, device=dev)
-            bnd[0] = True
-            for k in p.partition:
-                v = f.cols[k]
-                d = v.data[perm]
-                diff = d[1:] != d[:-1]
-                if v.valid is not None:
-                    vv = v.valid[perm]
-                    diff = (diff & vv[1:] & vv[:-1]) | (vv[1:] != vv[:-1])
-                bnd[1:] |= diff
+            native = perm.is_cuda
+            if native and p.partition:
+                bnd = self._key_change(f, p.partition, perm)
+            else:
+                bnd = torch.zeros(n, dtype=torch.bool, device=dev)
+                bnd[0] = True
+                for k in p.partition:
+                    v = f.cols[k]
+                    d = v.data[perm]
+                    diff = d[1:] != d[:-1]
+                    if v.valid is not None:
+                        vv = v.valid[perm]
+                        diff = (diff & vv[1:] & vv[:-1]) | (vv[1:] != vv[:-1])
+                    bnd[1:] |= diff
             seg = torch.cumsum(bnd.to(torch.int64), 0) - 1
             nseg = int(seg[-1].item()) + 1
             seg_start = torch.zeros(nseg, dtype=torch.int64, device=dev)
@@ -962,16 +975,21 @@ class Engine:
                 if fn == "row_number":
                     res_sorted = pos + 1
                 else:
-                    change = bnd.clone()
-                    for c, _asc in order:
-                        v = f.cols[c]
-                        d = v.data[perm]
-                        diff = d[1:] != d[:-1]
-                        if v.valid is not None:
-                            vv = v.valid[perm]
-                            diff = (diff & vv[1:] & vv[:-1]) | \
-                                (vv[1:] != vv[:-1])
-                        change[1:] |= diff
+                    if native:
+                        change = self._key_change(
+                            f, list(p.partition) + [c for c, _a in order],
+                            perm)
+                    else:
+                        change = bnd.clone()
+                        for c, _asc in order:
+                            v = f.cols[c]
+                            d = v.data[perm]
+                            diff = d[1:] != d[:-1]
+                            if v.valid is not None:
+                                vv = v.valid[perm]
+                                diff = (diff & vv[1:] & vv[:-1]) | \
+                                    (vv[1:] != vv[:-1])
+                            change[1:] |= diff
                     if fn == "rank":
                         idx = torch.arange(n, dtype=torch.int64, device=dev)
                         last_change = torch.cummax(
@@ -988,10 +1006,34 @@ class Engine:
                 raise ValueError(fn)
         return Frame(out, n, f.sharded)
 
+    @staticmethod
+    def _key_change(f: Frame, names, perm: torch.Tensor) -> torch.Tensor:
+        """Sorted-row boundary flags on the named columns (CUDA frames)."""
+        from ..ops.sort import key_change_flags
+        vals = [f.cols[k] for k in names]
+        return key_change_flags([v.data for v in vals], perm,
+                                [v.valid for v in vals])
+
     def _argsort(self, f: Frame, by: List[Tuple[str, bool]]) -> torch.Tensor:
-        """Stable multi-key argsort. Spark default null order: NULLS FIRST
-        when ascending, NULLS LAST when descending."""
+        """Stable multi-key argsort. Nulls come first in either direction:
+        the CPU expression below (the NDS oracle) fills them with the extreme
+        that its sort puts first, and the native path is told the same."""
         n = f.nrows
+        native = (n <= NATIVE_SORT_ANY_KEYS_ROWS or
+                  len(by) > TORCH_SORT_MAX_KEYS)
+        if by and native and f.cols[by[0][0]].data.is_cuda:
+            # one native packed-key sort; dictionary codes only sort the
+            # bits their dictionary needs
+            from ..ops.sort import sort_order_tensors
+            vals = [f.cols[name] for name, _asc in by]
+            return sort_order_tensors(
+                [v.data for v in vals], [v.valid for v in vals],
+                [asc for _name, asc in by], [True] * len(by),
+                key_bits=[None if v.dict is None or
+                          v.data.dtype.is_floating_point or
+                          v.data.dtype == torch.bool
+                          else max(1, (len(v.dict) - 1).bit_length())
+                          for v in vals])
         perm = torch.arange(n, dtype=torch.int64, device=self.device)
         for name, asc in reversed(by):
             v = f.cols[name]

@@ -1,1 +1,1 @@
-from . import aggregate, copying, hashing, join  # noqa: F401
+from . import aggregate, compact, copying, hashing, join, sort  # noqa: F401
