@@ -1,8 +1,5 @@
-"""Radix sort + sort-merge join (Java API parity:
+"""Sort order and sort-merge join (Java API parity:
 JoinPrimitives.sortMergeInnerJoin, join_primitives.hpp:64-72).
-
-Hand-written LSD radix sort for int64 keys (stable, 8-bit digits,
-wave-ballot multi-split — src/gpu/sort.hip); signed order via bias flip.
 
 Sort order (cudf sorted_order / sort_by_key): `sort_order_tensors`,
 `key_change_flags`, `sort_order` and `sort_by_key` give the stable,
@@ -14,6 +11,10 @@ is the same everywhere: nulls equal each other, all NaNs are equal (and sort
 above +inf), -0.0 == 0.0. CPU tensors take an equivalent torch expression;
 CUDA tensors always take the native kernels, with no host sync, so the ops
 run under stream capture.
+
+`sort_pairs_i64` is that sort with one ascending 64-bit signed key;
+`sort_merge_inner_join` sorts the build keys with it and probes them with the
+binary-search kernel of src/gpu/sort.hip.
 """
 from typing import List, Optional, Sequence, Tuple
 
@@ -21,47 +22,19 @@ import torch
 
 from .. import _native
 from ..columnar import Column, DType, Table, validity_to_bool
-
-EPB = 2048
+from .compact import nonzero
 
 
 def sort_pairs_i64(keys: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
     """Stable ascending sort; returns (sorted_keys, order) where
     sorted_keys[i] = keys[order[i]]."""
-    g = _native.gpu()
-    stream = _native.current_stream()
     n = keys.numel()
-    dev = keys.device
     if n == 0:
-        return keys.clone(), torch.empty(0, dtype=torch.int64, device=dev)
-    nblocks = (n + EPB - 1) // EPB
-    cur_k = torch.empty(n, dtype=torch.int64, device=dev)
-    g.bias_i64(keys.data_ptr(), n, cur_k.data_ptr(), stream)
-    cur_p = None
-    alt_k = torch.empty(n, dtype=torch.int64, device=dev)
-    alt_p = torch.empty(n, dtype=torch.int64, device=dev)
-    cur_p_t = torch.empty(n, dtype=torch.int64, device=dev)
-    hist = torch.empty(256 * nblocks, dtype=torch.int64, device=dev)
-    for pass_i in range(8):
-        shift = pass_i * 8
-        hist.zero_()
-        g.radix_hist(cur_k.data_ptr(), n, shift, nblocks, hist.data_ptr(),
-                     stream)
-        offsets = torch.zeros_like(hist)
-        torch.cumsum(hist[:-1], 0, out=offsets[1:])
-        g.radix_scatter(cur_k.data_ptr(),
-                        cur_p.data_ptr() if cur_p is not None else 0, n, shift,
-                        nblocks, offsets.data_ptr(), alt_k.data_ptr(),
-                        alt_p.data_ptr(), stream)
-        cur_k, alt_k = alt_k, cur_k
-        if cur_p is None:
-            cur_p = alt_p
-            alt_p = cur_p_t
-        else:
-            cur_p, alt_p = alt_p, cur_p
-    out_k = torch.empty(n, dtype=torch.int64, device=dev)
-    g.unbias_i64(cur_k.data_ptr(), n, out_k.data_ptr(), stream)
-    return out_k, cur_p
+        return keys.clone(), torch.empty(0, dtype=torch.int64,
+                                         device=keys.device)
+    key = _Key(keys, None, _SK_SINT, 64, desc=False, nulls_first=False)
+    order = _sort_order_keys([key], n, keys.device)
+    return keys[order], order
 
 
 def sort_merge_inner_join(build: Column, probe: Column):
@@ -72,19 +45,11 @@ def sort_merge_inner_join(build: Column, probe: Column):
     assert build.dtype == DType.INT64 and probe.dtype == DType.INT64
     dev = build.device
     bkeys = build.data
+    orig_rows = None
     if build.validity is not None:
-        # drop null build keys (never match)
-        from .join import HashJoinTable  # fall back for simplicity
-        keep = []
-        vals = build.to_pylist()
-        # null-aware compaction on device: use validity as mask via torch
-        import torch as _t
-        mask = _t.tensor([v is not None for v in vals], device=dev)
-        idx = mask.nonzero().view(-1)
-        bkeys = build.data[idx]
-        orig_rows = idx.to(_t.int64)
-    else:
-        orig_rows = None
+        # null build keys never match: sort the valid rows only
+        orig_rows = nonzero(validity_to_bool(build.validity, build.size))
+        bkeys = build.data[orig_rows]
     sorted_k, order = sort_pairs_i64(bkeys)
     build_rows = order if orig_rows is None else orig_rows[order]
     n = probe.size

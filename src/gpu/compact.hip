@@ -36,8 +36,6 @@ namespace srj {
 constexpr int COMPACT_TILE = 2048;                        // rows per tile
 constexpr int COMPACT_ROUNDS = COMPACT_TILE / DEFAULT_BLOCK;  // 8
 constexpr int COMPACT_WAVES = DEFAULT_BLOCK / WAVE;       // 4
-constexpr int COMPACT_SCAN_PER_THREAD = 4;
-constexpr int COMPACT_SCAN_CHUNK = DEFAULT_BLOCK * COMPACT_SCAN_PER_THREAD;
 constexpr int COMPACT_MAX_COLS = 16;
 
 static_assert(COMPACT_TILE % DEFAULT_BLOCK == 0, "tile is whole rounds");
@@ -110,39 +108,8 @@ __global__ __launch_bounds__(DEFAULT_BLOCK) void compact_scan_kernel(
     const int32_t* __restrict__ counts, int64_t ntiles,
     int64_t* __restrict__ offsets, int64_t* __restrict__ total) {
   __shared__ int64_t wtotal[COMPACT_WAVES];
-  const int tid = threadIdx.x;
-  const int wave = tid / WAVE;
-  const int lane = tid & (WAVE - 1);
-  int64_t carry = 0;
-  for (int64_t base = 0; base < ntiles; base += COMPACT_SCAN_CHUNK) {
-    const int64_t i0 = base + (int64_t)tid * COMPACT_SCAN_PER_THREAD;
-    int32_t c[COMPACT_SCAN_PER_THREAD];
-    int64_t local = 0;
-#pragma unroll
-    for (int k = 0; k < COMPACT_SCAN_PER_THREAD; ++k) {
-      c[k] = (i0 + k < ntiles) ? counts[i0 + k] : 0;
-      local += c[k];
-    }
-    int64_t incl = wave_prefix_incl<int64_t>(local);
-    if (lane == WAVE - 1) wtotal[wave] = incl;
-    __syncthreads();
-    int64_t wbase = 0, chunk_total = 0;
-#pragma unroll
-    for (int w = 0; w < COMPACT_WAVES; ++w) {
-      int64_t t = wtotal[w];
-      if (w < wave) wbase += t;
-      chunk_total += t;
-    }
-    int64_t run = carry + wbase + incl - local;
-#pragma unroll
-    for (int k = 0; k < COMPACT_SCAN_PER_THREAD; ++k) {
-      if (i0 + k < ntiles) offsets[i0 + k] = run;
-      run += c[k];
-    }
-    carry += chunk_total;
-    __syncthreads();  // wtotal is rewritten by the next chunk
-  }
-  if (tid == 0) *total = carry;
+  const int64_t kept = block_scan_chunked(counts, offsets, ntiles, wtotal);
+  if (threadIdx.x == 0) *total = kept;
 }
 
 // ---------------------------------------------------------------------------
@@ -323,7 +290,7 @@ extern "C" {
 
 int32_t srj_compact_tile_rows() { return COMPACT_TILE; }
 int32_t srj_compact_max_grid() { return (int32_t)MAX_GRID; }
-int32_t srj_compact_scan_chunk() { return COMPACT_SCAN_CHUNK; }
+int32_t srj_compact_scan_chunk() { return BLOCK_SCAN_CHUNK; }
 int32_t srj_compact_max_cols() { return COMPACT_MAX_COLS; }
 
 // count + scan: counts[ntiles] (int32 scratch), offsets[ntiles] exclusive

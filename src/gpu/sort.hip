@@ -1,136 +1,15 @@
-// Radix sort (LSD, 8-bit digits) + sort-merge join primitives.
+// Sort-merge join kernel.
 //
 // Reference parity: JoinPrimitives.sort_merge_inner_join
-// (join_primitives.hpp:64-72) — the reference leans on cub/cudf radix sort;
-// this is a fresh CDNA4 implementation:
-//   * stable LSD radix, 2048 elements per block (256 threads x 8/round),
-//     per-round wave-level multi-split via 8 x 64-bit ballots (no
-//     __match_any on CDNA; equality mask = AND of per-bit ballots),
-//     cross-wave rank through a [4][256] LDS wave-histogram,
-//     per-(block,digit) global bases from a host-side scan (torch.cumsum).
-//   * signed keys bias-flipped (x ^ 0x80..) so unsigned digit order sorts
-//     signed ascending.
-//   * sort_merge_inner_join: binary search of each probe row into the sorted
-//     build keys (lower/upper bound), two-phase count+emit with
-//     wave-aggregated output cursors.
+// (join_primitives.hpp:64-72). The build keys arrive sorted (the packed-key
+// radix sort of sort_order.hip, through ops/sort.py: sort_pairs_i64); each
+// probe row, sorted or not, binary-searches them (lower/upper bound) and the
+// matches are emitted in two phases, count then fill, with wave-aggregated
+// output cursors.
 #include "srj_common.hpp"
 
 namespace srj {
 
-constexpr int RADIX_BITS = 8;
-constexpr int RADIX = 256;
-constexpr int EPT = 8;                    // elements per thread per block
-constexpr int EPB = DEFAULT_BLOCK * EPT;  // 2048
-
-__device__ inline uint64_t bias_i64(int64_t v) {
-  return (uint64_t)v ^ 0x8000000000000000ull;
-}
-
-__global__ void radix_hist_kernel(const uint64_t* __restrict__ keys, int64_t n,
-                                  int32_t shift, int64_t nblocks,
-                                  int64_t* __restrict__ hist) {
-  __shared__ int lhist[RADIX];
-  for (int64_t b = blockIdx.x; b < nblocks; b += gridDim.x) {
-    for (int i = threadIdx.x; i < RADIX; i += blockDim.x) lhist[i] = 0;
-    __syncthreads();
-    int64_t base = b * EPB;
-    for (int r = 0; r < EPT; ++r) {
-      int64_t e = base + r * (int64_t)blockDim.x + threadIdx.x;
-      if (e < n) {
-        uint32_t d = (uint32_t)((keys[e] >> shift) & (RADIX - 1));
-        atomicAdd(lhist + d, 1);
-      }
-    }
-    __syncthreads();
-    // layout: hist[digit * nblocks + block] so a flat scan gives
-    // digit-major global offsets
-    for (int i = threadIdx.x; i < RADIX; i += blockDim.x) {
-      hist[(int64_t)i * nblocks + b] = lhist[i];
-    }
-    __syncthreads();
-  }
-}
-
-__global__ void radix_scatter_kernel(const uint64_t* __restrict__ keys,
-                                     const int64_t* __restrict__ payload,
-                                     int64_t n, int32_t shift, int64_t nblocks,
-                                     const int64_t* __restrict__ offsets,
-                                     uint64_t* __restrict__ out_keys,
-                                     int64_t* __restrict__ out_payload) {
-  __shared__ int counter[RADIX];          // block-running digit counts
-  __shared__ int wave_hist[4][RADIX];     // per-wave counts this round
-  __shared__ int64_t base_off[RADIX];     // global base per digit for block
-  for (int64_t b = blockIdx.x; b < nblocks; b += gridDim.x) {
-    for (int i = threadIdx.x; i < RADIX; i += blockDim.x) {
-      counter[i] = 0;
-      base_off[i] = offsets[(int64_t)i * nblocks + b];
-    }
-    for (int w = 0; w < 4; ++w)
-      for (int i = threadIdx.x; i < RADIX; i += blockDim.x) wave_hist[w][i] = 0;
-    __syncthreads();
-    int64_t base = b * EPB;
-    int wave = threadIdx.x / WAVE;
-    int lane = threadIdx.x & (WAVE - 1);
-    for (int r = 0; r < EPT; ++r) {
-      int64_t e = base + r * (int64_t)blockDim.x + threadIdx.x;
-      bool act = e < n;
-      uint64_t k = act ? keys[e] : 0;
-      uint32_t d = (uint32_t)((k >> shift) & (RADIX - 1));
-      // wave multi-split: equality mask across 64 lanes via 8 ballots
-      uint64_t eq = ~0ull;
-#pragma unroll
-      for (int bit = 0; bit < RADIX_BITS; ++bit) {
-        uint64_t bal = __ballot((d >> bit) & 1);
-        eq &= ((d >> bit) & 1) ? bal : ~bal;
-      }
-      uint64_t act_mask = __ballot(act);
-      eq &= act_mask;
-      uint32_t wave_rank = (uint32_t)__popcll(eq & ((1ull << lane) - 1));
-      bool leader = act && wave_rank == 0;
-      if (leader) wave_hist[wave][d] = (int)__popcll(eq);
-      __syncthreads();
-      if (act) {
-        int before = counter[d];
-        for (int w = 0; w < wave; ++w) before += wave_hist[w][d];
-        int64_t dst = base_off[d] + before + wave_rank;
-        out_keys[dst] = k;
-        if (out_payload) out_payload[dst] = payload ? payload[e] : e;
-      }
-      __syncthreads();
-      for (int i = threadIdx.x; i < RADIX; i += blockDim.x) {
-        int tot = 0;
-        for (int w = 0; w < 4; ++w) {
-          tot += wave_hist[w][i];
-          wave_hist[w][i] = 0;
-        }
-        counter[i] += tot;
-      }
-      __syncthreads();
-    }
-    __syncthreads();
-  }
-}
-
-__global__ void bias_kernel(const int64_t* __restrict__ in, int64_t n,
-                            uint64_t* __restrict__ out) {
-  int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
-       i += stride)
-    out[i] = bias_i64(in[i]);
-}
-
-__global__ void unbias_kernel(const uint64_t* __restrict__ in, int64_t n,
-                              int64_t* __restrict__ out) {
-  int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
-       i += stride)
-    out[i] = (int64_t)(in[i] ^ 0x8000000000000000ull);
-}
-
-// ---------------------------------------------------------------------------
-// sort-merge join: probe each row of (sorted or unsorted) probe keys against
-// SORTED build keys via binary search; two-phase count/emit.
-// ---------------------------------------------------------------------------
 template <bool FILL>
 __global__ void merge_join_kernel(const int64_t* __restrict__ build_sorted,
                                   const int64_t* __restrict__ build_rows,
@@ -198,32 +77,6 @@ __global__ void merge_join_kernel(const int64_t* __restrict__ build_sorted,
 using namespace srj;
 
 extern "C" {
-
-void srj_radix_hist(const uint64_t* keys, int64_t n, int32_t shift,
-                    int64_t nblocks, int64_t* hist, hipStream_t stream) {
-  int64_t g = nblocks < MAX_GRID ? nblocks : MAX_GRID;
-  radix_hist_kernel<<<g, DEFAULT_BLOCK, 0, stream>>>(keys, n, shift, nblocks,
-                                                     hist);
-}
-
-void srj_radix_scatter(const uint64_t* keys, const int64_t* payload, int64_t n,
-                       int32_t shift, int64_t nblocks, const int64_t* offsets,
-                       uint64_t* out_keys, int64_t* out_payload,
-                       hipStream_t stream) {
-  int64_t g = nblocks < MAX_GRID ? nblocks : MAX_GRID;
-  radix_scatter_kernel<<<g, DEFAULT_BLOCK, 0, stream>>>(
-      keys, payload, n, shift, nblocks, offsets, out_keys, out_payload);
-}
-
-void srj_bias_i64(const int64_t* in, int64_t n, uint64_t* out,
-                  hipStream_t stream) {
-  bias_kernel<<<grid_1d(n), DEFAULT_BLOCK, 0, stream>>>(in, n, out);
-}
-
-void srj_unbias_i64(const uint64_t* in, int64_t n, int64_t* out,
-                    hipStream_t stream) {
-  unbias_kernel<<<grid_1d(n), DEFAULT_BLOCK, 0, stream>>>(in, n, out);
-}
 
 void srj_merge_join(const int64_t* build_sorted, const int64_t* build_rows,
                     int64_t nbuild, const int64_t* probe, const uint8_t* pvalid,

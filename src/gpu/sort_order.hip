@@ -26,7 +26,7 @@
 //    workgroup per digit walking its row of block counts with a running
 //    carry. No kernel waits on another workgroup; no global atomics.
 //
-// MI355X notes: wave64 multi-split by 8 ballots as in sort.hip. The tile
+// MI355X notes: wave64 multi-split by 8 ballots (digit_peers). The tile
 // counts are written by one lane per distinct digit per wave and scanned by
 // one thread per digit, lanes on consecutive digits (conflict-free), with no
 // LDS atomics, so tie-heavy keys do not serialise on one counter. Key and
@@ -35,20 +35,14 @@
 #include "srj_common.hpp"
 #include "sort_order.hpp"
 
-extern "C" void srj_radix_hist(const uint64_t* keys, int64_t n, int32_t shift,
-                               int64_t nblocks, int64_t* hist,
-                               hipStream_t stream);
-
 namespace srj {
 
 constexpr int SORT_RADIX_BITS = 8;
 constexpr int SORT_RADIX = 256;
 constexpr int SORT_EPT = 8;
-constexpr int SORT_TILE = DEFAULT_BLOCK * SORT_EPT;  // 2048, sort.hip's EPB
+constexpr int SORT_TILE = DEFAULT_BLOCK * SORT_EPT;  // 2048
 constexpr int SORT_WAVES = DEFAULT_BLOCK / WAVE;     // 4
 constexpr int SORT_MAX_KEYS = 16;
-constexpr int SORT_SCAN_PER_THREAD = 4;
-constexpr int SORT_SCAN_CHUNK = DEFAULT_BLOCK * SORT_SCAN_PER_THREAD;
 
 static_assert(SORT_RADIX == DEFAULT_BLOCK, "one thread per digit");
 
@@ -232,8 +226,6 @@ __global__ __launch_bounds__(DEFAULT_BLOCK) void sort_small_kernel(
   static_assert(sizeof(TileCounts) * SORT_EPT <= sizeof(skey[0]),
                 "tile counts fit the idle key buffer");
   const int tid = threadIdx.x;
-  const int wave = tid / WAVE;
-  const int lane = tid & (WAVE - 1);
   const int rounds = (n + DEFAULT_BLOCK - 1) / DEFAULT_BLOCK;
 
   uint32_t actbits = 0;
@@ -268,14 +260,7 @@ __global__ __launch_bounds__(DEFAULT_BLOCK) void sort_small_kernel(
     // every row has the same digit: the order stays. The barrier also ends
     // the reads of the tile counts before skey[cur ^ 1] is written.
     if (__syncthreads_or(count == n)) continue;
-    int32_t incl = wave_prefix_incl<int32_t>(count);
-    if (lane == WAVE - 1) wave_tot[wave] = incl;
-    __syncthreads();
-    int32_t wbase = 0;
-#pragma unroll
-    for (int w = 0; w < SORT_WAVES; ++w)
-      if (w < wave) wbase += wave_tot[w];
-    digit_base[tid] = wbase + incl - count;
+    digit_base[tid] = block_scan_excl<int32_t>(count, wave_tot);
     __syncthreads();
 #pragma unroll
     for (int r = 0; r < SORT_EPT; ++r) {
@@ -296,6 +281,33 @@ __global__ __launch_bounds__(DEFAULT_BLOCK) void sort_small_kernel(
 }
 
 // ---------------------------------------------------------------------------
+// large path, histogram: digit counts of every tile by LDS atomics.
+// ---------------------------------------------------------------------------
+__global__ void radix_hist_kernel(const uint64_t* __restrict__ keys, int64_t n,
+                                  int32_t shift, int64_t nblocks,
+                                  int64_t* __restrict__ hist) {
+  __shared__ int lhist[SORT_RADIX];
+  for (int64_t b = blockIdx.x; b < nblocks; b += gridDim.x) {
+    for (int i = threadIdx.x; i < SORT_RADIX; i += blockDim.x) lhist[i] = 0;
+    __syncthreads();
+    int64_t base = b * SORT_TILE;
+    for (int r = 0; r < SORT_EPT; ++r) {
+      int64_t e = base + r * (int64_t)blockDim.x + threadIdx.x;
+      if (e < n) {
+        uint32_t d = (uint32_t)((keys[e] >> shift) & (SORT_RADIX - 1));
+        atomicAdd(lhist + d, 1);
+      }
+    }
+    __syncthreads();
+    // layout: hist[digit * nblocks + block], one row of block counts per digit
+    for (int i = threadIdx.x; i < SORT_RADIX; i += blockDim.x) {
+      hist[(int64_t)i * nblocks + b] = lhist[i];
+    }
+    __syncthreads();
+  }
+}
+
+// ---------------------------------------------------------------------------
 // large path, between histogram and scatter: workgroup d turns row d of the
 // digit-major hist[256][nblocks] into exclusive offsets within the digit, in
 // place, and writes the digit's total. Chunked with a running carry.
@@ -303,47 +315,16 @@ __global__ __launch_bounds__(DEFAULT_BLOCK) void sort_small_kernel(
 __global__ __launch_bounds__(DEFAULT_BLOCK) void sort_scan_rows_kernel(
     int64_t* __restrict__ hist, int64_t nblocks, int64_t* __restrict__ totals) {
   __shared__ int64_t wtotal[SORT_WAVES];
-  const int tid = threadIdx.x;
-  const int wave = tid / WAVE;
-  const int lane = tid & (WAVE - 1);
   for (int d = blockIdx.x; d < SORT_RADIX; d += gridDim.x) {
-    int64_t* __restrict__ row = hist + (int64_t)d * nblocks;
-    int64_t carry = 0;
-    for (int64_t base = 0; base < nblocks; base += SORT_SCAN_CHUNK) {
-      const int64_t i0 = base + (int64_t)tid * SORT_SCAN_PER_THREAD;
-      int64_t c[SORT_SCAN_PER_THREAD];
-      int64_t local = 0;
-#pragma unroll
-      for (int k = 0; k < SORT_SCAN_PER_THREAD; ++k) {
-        c[k] = (i0 + k < nblocks) ? row[i0 + k] : 0;
-        local += c[k];
-      }
-      int64_t incl = wave_prefix_incl<int64_t>(local);
-      if (lane == WAVE - 1) wtotal[wave] = incl;
-      __syncthreads();
-      int64_t wbase = 0, chunk_total = 0;
-#pragma unroll
-      for (int w = 0; w < SORT_WAVES; ++w) {
-        int64_t t = wtotal[w];
-        if (w < wave) wbase += t;
-        chunk_total += t;
-      }
-      int64_t run = carry + wbase + incl - local;
-#pragma unroll
-      for (int k = 0; k < SORT_SCAN_PER_THREAD; ++k) {
-        if (i0 + k < nblocks) row[i0 + k] = run;
-        run += c[k];
-      }
-      carry += chunk_total;
-      __syncthreads();  // wtotal is rewritten by the next chunk
-    }
-    if (tid == 0) totals[d] = carry;
+    int64_t* row = hist + (int64_t)d * nblocks;
+    const int64_t total = block_scan_chunked(row, row, nblocks, wtotal);
+    if (threadIdx.x == 0) totals[d] = total;
   }
 }
 
-// Sibling of sort.hip's radix_scatter_kernel: the per-(digit, block) offsets
-// are relative to the digit, and every block adds the 256 digit totals up in
-// LDS first. The payload is the running permutation (identity when null).
+// Large path, scatter: the per-(digit, block) offsets are relative to the
+// digit, and every block adds the 256 digit totals up in LDS first. The
+// payload is the running permutation (identity when null).
 __global__ __launch_bounds__(DEFAULT_BLOCK) void sort_scatter_kernel(
     const uint64_t* __restrict__ keys, const int64_t* __restrict__ payload,
     int64_t n, int32_t shift, int64_t nblocks,
@@ -354,19 +335,7 @@ __global__ __launch_bounds__(DEFAULT_BLOCK) void sort_scatter_kernel(
   __shared__ int64_t base_off[SORT_RADIX];
   __shared__ int64_t wtotal[SORT_WAVES];
   const int tid = threadIdx.x;
-  const int wave = tid / WAVE;
-  const int lane = tid & (WAVE - 1);
-  {
-    int64_t t = totals[tid];
-    int64_t incl = wave_prefix_incl<int64_t>(t);
-    if (lane == WAVE - 1) wtotal[wave] = incl;
-    __syncthreads();
-    int64_t wbase = 0;
-#pragma unroll
-    for (int w = 0; w < SORT_WAVES; ++w)
-      if (w < wave) wbase += wtotal[w];
-    digit_start[tid] = wbase + incl - t;
-  }
+  digit_start[tid] = block_scan_excl<int64_t>(totals[tid], wtotal);
   for (int64_t b = blockIdx.x; b < nblocks; b += gridDim.x) {
     base_off[tid] = digit_start[tid] + offsets[(int64_t)tid * nblocks + b];
     const int64_t base = b * SORT_TILE;
@@ -443,6 +412,13 @@ void srj_key_change_flags(const SortKey* keys, int32_t nkeys,
     key_change_kernel<<<grid_1d(n), DEFAULT_BLOCK, 0, stream>>>(
         a, perm, n, nrows, lo > 0 ? 1 : 0, out);
   }
+}
+
+void srj_radix_hist(const uint64_t* keys, int64_t n, int32_t shift,
+                    int64_t nblocks, int64_t* hist, hipStream_t stream) {
+  int64_t g = nblocks < MAX_GRID ? nblocks : MAX_GRID;
+  radix_hist_kernel<<<g, DEFAULT_BLOCK, 0, stream>>>(keys, n, shift, nblocks,
+                                                     hist);
 }
 
 // keys: every field of every word; word w owns keys [word_begin[w],

@@ -139,6 +139,67 @@ __device__ inline T wave_prefix_incl(T v) {
   return v;
 }
 
+// Exclusive prefix sum of v over the DEFAULT_BLOCK threads of a workgroup, in
+// thread order; every thread must call it. wtotal is LDS of the caller. With
+// `total`, *total is the sum over the workgroup (the same in every thread).
+// Barriers: exactly one, between the write of wtotal and its reads. The
+// caller owes a second one before wtotal is written again (the next call).
+template <typename T>
+__device__ __forceinline__ T block_scan_excl(T v,
+                                             T (&wtotal)[DEFAULT_BLOCK / WAVE],
+                                             T* total = nullptr) {
+  const int wave = threadIdx.x / WAVE;
+  const int lane = threadIdx.x & (WAVE - 1);
+  const T incl = wave_prefix_incl<T>(v);
+  if (lane == WAVE - 1) wtotal[wave] = incl;
+  __syncthreads();
+  T wbase = 0, sum = 0;
+#pragma unroll
+  for (int w = 0; w < DEFAULT_BLOCK / WAVE; ++w) {
+    const T t = wtotal[w];
+    if (w < wave) wbase += t;
+    sum += t;
+  }
+  if (total) *total = sum;
+  return wbase + incl - v;
+}
+
+// Exclusive prefix sum of in[0, n) into out[0, n) by ONE workgroup of
+// DEFAULT_BLOCK threads: chunks of BLOCK_SCAN_CHUNK items, BLOCK_SCAN_PER_THREAD
+// consecutive items per thread, a running carry between chunks. Returns the
+// total in every thread. out may alias in: a thread reads its items of a chunk
+// before the chunk's first barrier and writes the same positions after it.
+// Ends with a barrier, so wtotal is free for reuse on return.
+constexpr int BLOCK_SCAN_PER_THREAD = 4;
+constexpr int BLOCK_SCAN_CHUNK = DEFAULT_BLOCK * BLOCK_SCAN_PER_THREAD;
+
+template <typename In>
+__device__ __forceinline__ int64_t block_scan_chunked(
+    const In* in, int64_t* out, int64_t n,
+    int64_t (&wtotal)[DEFAULT_BLOCK / WAVE]) {
+  int64_t carry = 0;
+  for (int64_t base = 0; base < n; base += BLOCK_SCAN_CHUNK) {
+    const int64_t i0 = base + (int64_t)threadIdx.x * BLOCK_SCAN_PER_THREAD;
+    In c[BLOCK_SCAN_PER_THREAD];
+    int64_t local = 0;
+#pragma unroll
+    for (int k = 0; k < BLOCK_SCAN_PER_THREAD; ++k) {
+      c[k] = (i0 + k < n) ? in[i0 + k] : 0;
+      local += c[k];
+    }
+    int64_t chunk_total;
+    int64_t run = carry + block_scan_excl<int64_t>(local, wtotal, &chunk_total);
+#pragma unroll
+    for (int k = 0; k < BLOCK_SCAN_PER_THREAD; ++k) {
+      if (i0 + k < n) out[i0 + k] = run;
+      run += c[k];
+    }
+    carry += chunk_total;
+    __syncthreads();  // wtotal is rewritten by the next chunk
+  }
+  return carry;
+}
+
 template <typename T>
 __device__ inline T wave_max(T v) {
 #pragma unroll

@@ -266,48 +266,128 @@ def test_truncate_timestamp():
     assert truncate_timestamp(col, "DAY").to_pylist()[1] is None
 
 
+_I64 = torch.iinfo(torch.int64)
+
+
+def _check_sort_pairs(t):
+    """sorted keys and order both equal torch's stable sort, exactly."""
+    from spark_rapids_jni_amd.ops.sort import sort_pairs_i64
+    sk, order = sort_pairs_i64(t)
+    ref, ref_idx = torch.sort(t, stable=True)
+    assert order.dtype == torch.int64
+    assert torch.equal(sk, ref)
+    assert torch.equal(order, ref_idx)
+    assert torch.equal(t[order], sk)
+
+
 @pytest.mark.gpu
 def test_radix_sort_i64():
-    from spark_rapids_jni_amd.ops.sort import sort_pairs_i64
-    for n in [0, 1, 63, 2048, 5000, 100000]:
-        t = torch.randint(-2**62, 2**62, (n,), dtype=torch.int64, device="cuda")
-        if n > 10:
-            t[:5] = torch.tensor([0, -1, 1, -2**62, 2**62 - 1], device="cuda")
-        sk, order = sort_pairs_i64(t)
-        ref, ref_idx = torch.sort(t, stable=True)
-        assert torch.equal(sk, ref), f"n={n}"
-        assert torch.equal(t[order], sk), f"n={n} payload"
+    g = torch.Generator(device="cuda")
+    g.manual_seed(63)
+    # the extremes and the neighbours of the sign flip, twice each so that
+    # ties occur, spread from the first row to the last
+    plant = torch.tensor([_I64.min, _I64.max, -1, 0, 1] * 2, device="cuda")
+    # 2048 is the switch from one workgroup to tiles; above it a second tile
+    # and a partial last tile
+    for n in [0, 1, 63, 64, 65, 2047, 2048, 2049, 4097, 100000]:
+        t = torch.randint(-2**62, 2**62, (n,), dtype=torch.int64,
+                          device="cuda", generator=g)
+        if n >= plant.numel():
+            at = torch.arange(plant.numel(), device="cuda") * (n - 1) // 9
+            t[at] = plant
+        elif n:
+            t[:] = plant[:n]
+        _check_sort_pairs(t)
 
 
 @pytest.mark.gpu
 def test_radix_sort_stability():
-    from spark_rapids_jni_amd.ops.sort import sort_pairs_i64
-    t = torch.tensor([5, 3, 5, 3, 5, 3] * 700, dtype=torch.int64,
-                     device="cuda")
-    sk, order = sort_pairs_i64(t)
-    oh = order.cpu().tolist()
-    threes = [i for i in oh[:2100]]
-    assert threes == sorted(threes)  # stable: original order preserved
-    fives = [i for i in oh[2100:]]
-    assert fives == sorted(fives)
+    # tie-heavy: 3 distinct values over a second, partial tile
+    t = torch.tensor([5, -3, _I64.max] * 1366, dtype=torch.int64,
+                     device="cuda")[:4097]
+    _check_sort_pairs(t)
+    # every pass sees a single digit
+    _check_sort_pairs(torch.full((2049,), -7, dtype=torch.int64,
+                                 device="cuda"))
 
 
 @pytest.mark.gpu
-def test_sort_merge_join_matches_hash_join():
+def test_radix_sort_i64_graph_capture():
+    """sort_pairs_i64 allocates no per-pass scratch and never syncs, so it
+    records into a graph; the replay sorts what the input buffer then holds."""
+    from spark_rapids_jni_amd.ops.sort import sort_pairs_i64
+    n = 2049
+    gen = torch.Generator(device="cuda")
+    gen.manual_seed(11)
+    t = torch.zeros(n, dtype=torch.int64, device="cuda")
+    sort_pairs_i64(t)  # warm up outside the capture
+    torch.cuda.synchronize()
+    side = torch.cuda.Stream()
+    graph = torch.cuda.CUDAGraph()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        with torch.cuda.graph(graph, stream=side):
+            sk, order = sort_pairs_i64(t)
+    torch.cuda.current_stream().wait_stream(side)
+    fresh = torch.randint(-2**63, 2**63 - 1, (n,), dtype=torch.int64,
+                          device="cuda", generator=gen)
+    fresh[:5] = torch.tensor([_I64.min, _I64.max, -1, 0, 1], device="cuda")
+    t.copy_(fresh)
+    graph.replay()
+    torch.cuda.synchronize()
+    ref, ref_idx = torch.sort(fresh, stable=True)
+    assert torch.equal(sk, ref)
+    assert torch.equal(order, ref_idx)
+
+
+def _check_sort_merge_join(bvals, pvals):
     from spark_rapids_jni_amd.ops.join import HashJoinTable
     from spark_rapids_jni_amd.ops.sort import sort_merge_inner_join
-    import random as rnd
-    rnd.seed(3)
-    bvals = [rnd.randint(0, 500) if rnd.random() > 0.02 else None
-             for _ in range(1500)]
-    pvals = [rnd.randint(0, 600) if rnd.random() > 0.02 else None
-             for _ in range(4000)]
     b = Column.from_pylist(bvals, DType.INT64, "cuda")
     p = Column.from_pylist(pvals, DType.INT64, "cuda")
     sb, sp = sort_merge_inner_join(b, p)
     hb, hp = HashJoinTable.build(b).inner_join(p)
     assert set(zip(sb.cpu().tolist(), sp.cpu().tolist())) == \
         set(zip(hb.cpu().tolist(), hp.cpu().tolist()))
+    return b, p
+
+
+@pytest.mark.gpu
+def test_sort_merge_join_matches_hash_join():
+    import random as rnd
+    rnd.seed(3)
+    bvals = [rnd.randint(0, 500) if rnd.random() > 0.02 else None
+             for _ in range(1500)]
+    pvals = [rnd.randint(0, 600) if rnd.random() > 0.02 else None
+             for _ in range(4000)]
+    _check_sort_merge_join(bvals, pvals)
+
+
+@pytest.mark.gpu
+def test_sort_merge_join_build_nulls_stay_on_device(monkeypatch):
+    """Nulls at the first and last build row, none on the probe side; the
+    join must not read the build column back through Column.to_pylist."""
+    from spark_rapids_jni_amd.ops.sort import sort_merge_inner_join
+    import random as rnd
+    rnd.seed(5)
+    n = 1500
+    bvals = [rnd.randint(0, 500) for _ in range(n)]
+    bvals[0] = bvals[n - 1] = None
+    pvals = [rnd.randint(0, 600) for _ in range(4000)]
+    pvals[7] = 0  # the value a null build row holds in its data buffer
+    b, p = _check_sort_merge_join(bvals, pvals)
+    assert p.validity is None
+
+    def no_host_read(self):
+        raise AssertionError("Column.to_pylist called")
+
+    with monkeypatch.context() as m:
+        m.setattr(Column, "to_pylist", no_host_read)
+        sb, sp = sort_merge_inner_join(b, p)
+    assert sb.numel() > 0
+    got = sb.cpu().tolist()
+    assert 0 not in got and n - 1 not in got  # a null build key never matches
+    assert torch.equal(b.data[sb.long()], p.data[sp])
 
 
 @pytest.mark.gpu
