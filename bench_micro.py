@@ -190,6 +190,45 @@ def sort_order_bench(n, iters, dev, g):
             print(json.dumps(rec), flush=True)
 
 
+def join_narrow_bench(nb, npr, iters, dev, g):
+    """Narrow (8-byte slot) against wide (16-byte slot) join table on the same
+    dense int64 keys, build and probe timed separately and alternating. The
+    build time includes the zero fill of the table and, for the automatic
+    narrow choice, the min/max scan with its read-back."""
+    from spark_rapids_jni_amd.columnar import Column, DType
+    from spark_rapids_jni_amd.ops.join import HashJoinTable
+    bcol = Column(DType.INT64, nb, torch.randperm(nb, dtype=torch.int64,
+                                                  device=dev, generator=g))
+    pcol = Column(DType.INT64, npr, torch.randint(
+        0, 2 * nb, (npr,), dtype=torch.int64, device=dev, generator=g))
+    tables = {}
+
+    def build(narrow):
+        def run():
+            tables[narrow] = None  # one table resident at a time
+            tables[narrow] = HashJoinTable.build(bcol, narrow=narrow)
+        return run
+
+    def probe(narrow):
+        return lambda: tables[narrow].inner_join(pcol, out_hint=npr)
+
+    for phase, fn in (("build", build), ("probe", probe)):
+        rows = nb if phase == "build" else npr
+        if phase == "probe":
+            tables[True] = HashJoinTable.build(bcol, narrow=True)
+            tables[False] = HashJoinTable.build(bcol, narrow=False)
+        nar, wide = ab_time(fn(True), fn(False), iters, repeats=3)
+        for path, xs in (("narrow", nar), ("wide", wide)):
+            xs = sorted(xs)
+            print(json.dumps({
+                "bench": f"join_narrow_{phase}", "path": path,
+                "build_rows": nb, "probe_rows": npr,
+                "ms": round(xs[1] * 1e3, 4), "ms_min": round(xs[0] * 1e3, 4),
+                "ms_max": round(xs[2] * 1e3, 4),
+                "rows_per_sec": round(rows / xs[1], 1)}), flush=True)
+    tables.clear()
+
+
 def plumbing_bench():
     """BASELINE config[0]: murmur3 + row<->columnar on a 1k-row int64 batch
     via the HOST path (no GPU) — measures binding/plumbing overhead like the
@@ -220,7 +259,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=2**24)
     ap.add_argument("--iters", type=int, default=5)
-    ap.add_argument("--only", choices=["sort_order"], default=None,
+    ap.add_argument("--only", choices=["sort_order", "join_narrow"],
+                    default=None,
                     help="run just this group")
     args = ap.parse_args()
     if args.only == "sort_order":
@@ -228,6 +268,13 @@ def main():
         g.manual_seed(7)
         for sn in (256, 2048, 2**16, args.rows):
             sort_order_bench(sn, 20, "cuda", g)
+        return
+    if args.only == "join_narrow":
+        g = torch.Generator(device="cuda")
+        g.manual_seed(7)
+        # beyond the Infinity Cache, then cache resident
+        for nb, npr in ((2**26, 2**26), (2**20, 2**24)):
+            join_narrow_bench(nb, npr, args.iters, "cuda", g)
         return
     plumbing_bench()  # CPU shape (BASELINE config[0]) first
     n = args.rows

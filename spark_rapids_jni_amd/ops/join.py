@@ -36,9 +36,10 @@ _FAST_KEY_DTYPES = None
 
 
 def _is_i64_fast(cols: List[Column]) -> bool:
-    """Single integer-typed key -> the specialized 16B-slot table (narrower
-    ints are upcast to int64 once; sign extension preserves equality, and
-    real NDS surrogate keys are INT32)."""
+    """Single integer-typed key -> the specialized fast-path tables: the
+    narrow one reads 4-byte-or-less columns in place (real NDS surrogate
+    keys are INT32); the wide one upcasts them to int64 once, where sign
+    extension preserves equality."""
     global _FAST_KEY_DTYPES
     from ..columnar import DType
     if _FAST_KEY_DTYPES is None:
@@ -53,6 +54,39 @@ def _as_i64_keys(c: Column) -> Column:
         return c
     return Column(c.dtype, c.size, c.data.to(torch.int64), c.validity,
                   null_count=None)
+
+
+# int64 / timestamp keys are range-scanned for the narrow table only from this
+# build size on: from here the wide table, next_pow2(4n) x 16 B, no longer
+# fits the 256 MiB Infinity Cache, and below it the scan's host read-back is
+# not worth paying in host-bound plans.
+NARROW_SCAN_MIN_ROWS = 1 << 22
+# slots per build row before rounding up to a power of two (25% max load)
+NARROW_SLOTS_PER_ROW = 4
+_I32_KMIN = -(1 << 31)
+
+
+def _fits_narrow(lo: int, hi: int) -> bool:
+    """True when every key of [lo, hi] has a 32-bit offset from lo."""
+    return hi - lo < (1 << 32)
+
+
+def _key_range(data: torch.Tensor) -> Tuple[int, int]:
+    """(min, max) of a key tensor as Python ints: one pass, one read-back."""
+    lo, hi = torch.aminmax(data)
+    lo, hi = torch.stack([lo, hi]).cpu().tolist()
+    return int(lo), int(hi)
+
+
+def _narrow_keys(c: Column) -> Tuple[torch.Tensor, int]:
+    """(key tensor the narrow kernels read in place, key_i32 flag): 4-byte
+    columns as they are, 1- and 2-byte ones widened to int32."""
+    d = c.data
+    if d.dtype == torch.int64:
+        return d, 0
+    if d.dtype != torch.int32:
+        d = d.to(torch.int32)
+    return d, 1
 
 
 def _int_packable(cols: List[Column]) -> bool:
@@ -113,55 +147,105 @@ class HashJoinTable:
     """Build-side hash table reusable across probes (reference: the build/probe
     split of hash_inner_join).
 
-    Two layouts: a generic (fingerprint32|row+1) single-word table for any key
-    schema, and a specialized 16-byte {key,row} table for single-int64 keys
-    (the NDS surrogate-key hot path) with software-pipelined probing — see
-    src/gpu/hashtable_i64.hip.
+    Three layouts (`layout`): "generic", a (fingerprint32|row+1) single-word
+    table for any key schema; "wide", the specialized 16-byte {key,row} table
+    for single integer keys that need 64 bits; and "narrow", one 8-byte word
+    (key - kmin | row+1 | chain) per slot for keys whose range fits 32 bits —
+    INT32/DATE32 columns, packed tuples, dense int64 surrogate keys. Wide and
+    narrow are the software-pipelined fast path (`i64_fast`), see
+    src/gpu/hashtable_i64.hip. `capacity` is the slot count in every layout.
     """
 
     def __init__(self, build_keys: List[Column], slots: torch.Tensor,
-                 capacity: int, keep, i64_fast: bool):
+                 capacity: int, keep, i64_fast: bool,
+                 layout: Optional[str] = None, kmin: int = 0):
         self.build_keys = build_keys
         self.slots = slots
         self.capacity = capacity
         self._keep = keep
         self.i64_fast = i64_fast
+        self.layout = layout or ("wide" if i64_fast else "generic")
+        self.kmin = kmin
         self.num_build_rows = build_keys[0].size
 
     @staticmethod
     def build(keys: Union[Column, Table, Sequence[Column]],
-              force_generic: bool = False) -> "HashJoinTable":
+              force_generic: bool = False,
+              narrow: Optional[bool] = None) -> "HashJoinTable":
+        """narrow: True forces the 8-byte-slot table (raises if the key range
+        does not fit 32 bits), False forbids it, None decides: 4-byte-or-less
+        key columns and packed tuples of width product <= 2^32 always, int64
+        columns from NARROW_SCAN_MIN_ROWS rows when a min/max scan fits."""
         cols = _keys(keys)
         n = cols[0].size
         assert n < 2**31, "build side capped at 2^31-1 rows (chunk the build)"
         g = _native.gpu()
         dev = cols[0].device
+        stream = _native.current_stream()
         # int64 fast path runs at 25% max load: random-probe scans touch
         # ~1.3 slots instead of ~2.5 at 50% load (measured faster than
         # double-slot prefetching); generic path stays at 50%.
         capacity = max(_next_pow2(n * 2), 64)
+
+        def build_narrow(data, key_i32, valid, kmin, keep, pack=None):
+            cap = max(_next_pow2(n * NARROW_SLOTS_PER_ROW), 64)
+            slots = torch.zeros(cap, dtype=torch.int64, device=dev)
+            g.join_build_n32(data.data_ptr(), key_i32,
+                             valid.data_ptr() if valid is not None else 0,
+                             n, slots.data_ptr(), cap, kmin, stream)
+            tbl = HashJoinTable(cols, slots, cap, keep, True, "narrow", kmin)
+            if pack is not None:
+                tbl._pack = pack
+            return tbl
+
         pack = None
         if not force_generic and _int_packable(cols):
             pack = _pack_ranges(cols)
         if pack is not None:
             packed, pvalid = _pack_keys(cols, *pack)
+            total = 1
+            for w in pack[1]:
+                total *= w
+            fits = total <= (1 << 32)
+            if narrow and not fits:
+                raise ValueError("narrow=True: packed key range needs more "
+                                 "than 32 bits")
+            if fits and narrow is not False:
+                return build_narrow(packed, 0, pvalid, 0, (packed, pvalid),
+                                    pack)
             capacity = max(_next_pow2(n * 4), 64)
             slots = torch.zeros(capacity * 2, dtype=torch.int64, device=dev)
             g.join_build_i64(packed.data_ptr(),
                              pvalid.data_ptr() if pvalid is not None else 0,
-                             n, slots.data_ptr(), capacity,
-                             _native.current_stream())
+                             n, slots.data_ptr(), capacity, stream)
             tbl = HashJoinTable(cols, slots, capacity, (packed, pvalid), True)
             tbl._pack = pack
             return tbl
         if _is_i64_fast(cols) and not force_generic:
+            c0 = cols[0]
+            if narrow is not False:
+                if c0.data.dtype != torch.int64:
+                    # range known from the type: no scan, no sync
+                    data, key_i32 = _narrow_keys(c0)
+                    return build_narrow(data, key_i32, c0.validity, _I32_KMIN,
+                                        data)
+                if narrow or n >= NARROW_SCAN_MIN_ROWS:
+                    lo, hi = _key_range(c0.data) if n else (0, 0)
+                    if _fits_narrow(lo, hi):
+                        return build_narrow(c0.data, 0, c0.validity, lo, None)
+                    if narrow:
+                        raise ValueError(
+                            f"narrow=True: key range [{lo}, {hi}] needs more "
+                            "than 32 bits")
             capacity = max(_next_pow2(n * 4), 64)
-            c = _as_i64_keys(cols[0])
+            c = _as_i64_keys(c0)
             slots = torch.zeros(capacity * 2, dtype=torch.int64, device=dev)
             g.join_build_i64(c.data.data_ptr(),
                              c.validity.data_ptr() if c.validity is not None else 0,
-                             n, slots.data_ptr(), capacity, _native.current_stream())
+                             n, slots.data_ptr(), capacity, stream)
             return HashJoinTable(cols, slots, capacity, None, True)
+        if narrow:
+            raise ValueError("narrow=True needs integer keys on the fast path")
         slots = torch.zeros(capacity, dtype=torch.int64, device=dev)
         desc, top, keep = pack_descriptors(cols)
         g.join_build(desc.data_ptr(), top.data_ptr(), len(cols), n,
@@ -173,6 +257,40 @@ class HashJoinTable:
         pdesc, ptop, pkeep = pack_descriptors(probe_cols)
         return bdesc, btop, pdesc, ptop, (bkeep, pkeep, bdesc, btop, pdesc, ptop)
 
+    def _fast_probe_col(self, pcols: List[Column]) -> Optional[Column]:
+        """The single key column the fast-path probe kernels read, or None
+        when this probe has to take the generic kernels."""
+        pack = getattr(self, "_pack", None)
+        if not self.i64_fast:
+            return None
+        if pack is not None:
+            if len(pcols) != len(self.build_keys):
+                return None
+            packed, pvalid = _pack_keys(pcols, *pack)
+            return Column(pcols[0].dtype, pcols[0].size, packed, pvalid,
+                          null_count=None)
+        if not _is_i64_fast(pcols):
+            return None
+        if self.layout == "narrow":
+            return pcols[0]  # read in place, whatever its integer width
+        return _as_i64_keys(pcols[0])
+
+    def _probe_fast(self, p: Column, counter, out_build, out_probe,
+                    out_capacity, matched, fill, stream):
+        g = _native.gpu()
+        pvalid = p.validity.data_ptr() if p.validity is not None else 0
+        if self.layout == "narrow":
+            data, key_i32 = _narrow_keys(p)
+            g.join_probe_n32(data.data_ptr(), key_i32, pvalid, p.size,
+                             self.slots.data_ptr(), self.capacity, self.kmin,
+                             counter.data_ptr(), out_build, out_probe,
+                             out_capacity, matched, fill, 0, stream)
+        else:
+            g.join_probe_i64(p.data.data_ptr(), pvalid, p.size,
+                             self.slots.data_ptr(), self.capacity,
+                             counter.data_ptr(), out_build, out_probe,
+                             out_capacity, matched, fill, 0, stream)
+
     def inner_join(self, probe: Union[Column, Table, Sequence[Column]],
                    out_hint: Optional[int] = None,
                    track_build_matches: bool = False):
@@ -182,16 +300,8 @@ class HashJoinTable:
         g = _native.gpu()
         stream = _native.current_stream()
         dev = pcols[0].device
-        pack = getattr(self, "_pack", None)
-        fast = self.i64_fast and (
-            (pack is not None and len(pcols) == len(self.build_keys))
-            or (pack is None and _is_i64_fast(pcols)))
-        if fast and pack is not None:
-            packed, pvalid = _pack_keys(pcols, *pack)
-            pcols = [Column(pcols[0].dtype, nprobe, packed, pvalid,
-                            null_count=None)]
-        elif fast:
-            pcols = [_as_i64_keys(pcols[0])]
+        p = self._fast_probe_col(pcols)
+        fast = p is not None
         counter = torch.zeros(1, dtype=torch.int64, device=dev)
         if not fast:
             bdesc, btop, pdesc, ptop, keep = self._descs(pcols)
@@ -202,15 +312,9 @@ class HashJoinTable:
         # scatter adds 29 ms/chunk (profiles/r01_bench_join_22.1B.json).
         # The kernels stay exposed (g.part_hist/part_scatter, idxmap probe)
         # for schema-partitioned shuffle use; the probe here stays direct.
-        probe_keys_ptr = pcols[0].data.data_ptr() if fast else 0
-        idxmap_ptr = 0
         if out_hint is None:
             if fast:
-                p = pcols[0]
-                g.join_probe_i64(probe_keys_ptr,
-                                 p.validity.data_ptr() if p.validity is not None else 0,
-                                 nprobe, self.slots.data_ptr(), self.capacity,
-                                 counter.data_ptr(), 0, 0, 0, 0, 0, 0, stream)
+                self._probe_fast(p, counter, 0, 0, 0, 0, 0, stream)
             else:
                 g.join_probe_count(bdesc.data_ptr(), btop.data_ptr(), pdesc.data_ptr(),
                                    ptop.data_ptr(), len(pcols), nprobe,
@@ -225,14 +329,10 @@ class HashJoinTable:
         matched = (torch.zeros(self.num_build_rows, dtype=torch.uint8, device=dev)
                    if track_build_matches else None)
         if fast:
-            p = pcols[0]
-            g.join_probe_i64(probe_keys_ptr,
-                             p.validity.data_ptr() if p.validity is not None else 0,
-                             nprobe, self.slots.data_ptr(), self.capacity,
-                             counter.data_ptr(), out_build.data_ptr(),
+            self._probe_fast(p, counter, out_build.data_ptr(),
                              out_probe.data_ptr(), total,
                              matched.data_ptr() if matched is not None else 0,
-                             1, idxmap_ptr, stream)
+                             1, stream)
         else:
             g.join_probe_fill(bdesc.data_ptr(), btop.data_ptr(), pdesc.data_ptr(),
                               ptop.data_ptr(), len(pcols), nprobe,
@@ -264,24 +364,10 @@ class HashJoinTable:
         matched = torch.zeros(self.num_build_rows, dtype=torch.uint8,
                               device=dev)
         counter = torch.zeros(1, dtype=torch.int64, device=dev)
-        pack = getattr(self, "_pack", None)
-        fast = self.i64_fast and (
-            (pack is not None and len(pcols) == len(self.build_keys))
-            or (pack is None and _is_i64_fast(pcols)))
-        if fast and pack is not None:
-            packed, pvalid = _pack_keys(pcols, *pack)
-            pcols = [Column(pcols[0].dtype, nprobe, packed, pvalid,
-                            null_count=None)]
-        elif fast:
-            pcols = [_as_i64_keys(pcols[0])]
-        if fast:
-            p = pcols[0]
-            g.join_probe_i64(p.data.data_ptr(),
-                             p.validity.data_ptr() if p.validity is not None
-                             else 0,
-                             nprobe, self.slots.data_ptr(), self.capacity,
-                             counter.data_ptr(), 0, 0, 0,
-                             matched.data_ptr(), 1, 0, stream)
+        p = self._fast_probe_col(pcols)
+        if p is not None:
+            self._probe_fast(p, counter, 0, 0, 0, matched.data_ptr(), 1,
+                             stream)
         else:
             bdesc, btop, pdesc, ptop, keep = self._descs(pcols)
             g.join_probe_fill(bdesc.data_ptr(), btop.data_ptr(),

@@ -16,6 +16,8 @@
 //     first-match case), per-match atomics only for rare duplicate matches.
 // Claim protocol: atomicCAS on the row word (0 = empty), winner writes key;
 // no sentinel key needed, build completes before probe launches.
+// Keys whose range fits 32 bits take the narrow table further down instead:
+// the same pipeline over 8-byte slots claimed and published by one CAS.
 #include "srj_common.hpp"
 #include "agg_common.hpp"
 
@@ -128,6 +130,8 @@ __global__ void join_probe_i64_kernel(
   int64_t nthreads = (int64_t)gridDim.x * blockDim.x;
   int lane = threadIdx.x & (WAVE - 1);
   uint64_t count_local = 0;
+  const longlong2* __restrict__ slots2 =
+      reinterpret_cast<const longlong2*>(slots);  // {key, row1} in one load
   int64_t nbatch = (nprobe + (int64_t)PPIPE - 1) / PPIPE;
   // pad so every lane of a wave runs the same iterations (wave shuffles)
   int64_t nbatch_pad = (nbatch + WAVE - 1) & ~(int64_t)(WAVE - 1);
@@ -146,7 +150,11 @@ __global__ void join_probe_i64_kernel(
     if (!batch_ok) vbits = 0;
     long long k[PPIPE];
     uint64_t s[PPIPE];
-    Slot64 first[PPIPE];
+    // the fetched slot lives in two scalar arrays and the first chain step is
+    // peeled out of the walk below: a `cur = first[b]` / `cur = slots[sl]`
+    // loop merges a private-array pointer with a global one, which kept the
+    // whole array in scratch (a store and a flat load per row)
+    long long fk[PPIPE], fr[PPIPE];
 #pragma unroll
     for (int b = 0; b < PPIPE; ++b) {
       int64_t row = base + b;
@@ -154,7 +162,11 @@ __global__ void join_probe_i64_kernel(
       s[b] = slot_of(i64_hash(k[b]), mask);
     }
 #pragma unroll
-    for (int b = 0; b < PPIPE; ++b) first[b] = slots[s[b]];
+    for (int b = 0; b < PPIPE; ++b) {
+      longlong2 v = slots2[s[b]];
+      fk[b] = v.x;
+      fr[b] = v.y;
+    }
     // resolve: count matches; carry the FIRST match's build row in a
     // register so the (overwhelmingly common) exactly-one-match case emits
     // without re-walking the slot chain
@@ -165,17 +177,23 @@ __global__ void join_probe_i64_kernel(
     for (int b = 0; b < PPIPE; ++b) {
       nmb[b] = 0;
       hit1[b] = 0;
-      if (!((vbits >> b) & 1)) continue;
-      Slot64 cur = first[b];
-      uint64_t sl = s[b];
-      while (cur.row1 != 0) {
-        if (cur.key == k[b]) {
-          if (nmb[b] == 0) hit1[b] = cur.row1 & SLOT_ROW;
-          ++nmb[b];
+      if (!((vbits >> b) & 1) || fr[b] == 0) continue;
+      if (fk[b] == k[b]) {
+        hit1[b] = fr[b] & SLOT_ROW;
+        nmb[b] = 1;
+      }
+      if (fr[b] & SLOT_CHAIN) {
+        uint64_t sl = s[b];
+        while (true) {
+          sl = (sl + 1) & mask;
+          longlong2 v = slots2[sl];
+          if (v.y == 0) break;
+          if (v.x == k[b]) {
+            if (nmb[b] == 0) hit1[b] = v.y & SLOT_ROW;
+            ++nmb[b];
+          }
+          if (!(v.y & SLOT_CHAIN)) break;  // chain ends here
         }
-        if (!(cur.row1 & SLOT_CHAIN)) break;  // chain ends here
-        sl = (sl + 1) & mask;
-        cur = slots[sl];
       }
       nm += nmb[b];
     }
@@ -196,10 +214,11 @@ __global__ void join_probe_i64_kernel(
 #pragma unroll
       for (int b = 0; b < PPIPE; ++b) {
         if (nmb[b] == 0) continue;
+        int64_t prow = idxmap ? (int64_t)idxmap[base + b] : base + b;
         if (nmb[b] == 1) {
           if (pos < out_capacity) {
             out_build[pos] = (int32_t)(hit1[b] - 1);
-            out_probe[pos] = idxmap ? (int64_t)idxmap[base + b] : base + b;
+            out_probe[pos] = prow;
           }
           // matched flags are valid even when the pair output overflows
           // (capacity-0 mark-only probes depend on this)
@@ -207,21 +226,230 @@ __global__ void join_probe_i64_kernel(
           ++pos;
           continue;
         }
-        Slot64 cur = first[b];
-        uint64_t sl = s[b];
-        while (cur.row1 != 0) {
-          if (cur.key == k[b]) {
-            long long r1 = cur.row1 & SLOT_ROW;
-            if (pos < out_capacity) {
-              out_build[pos] = (int32_t)(r1 - 1);
-              out_probe[pos] = idxmap ? (int64_t)idxmap[base + b] : base + b;
-            }
-            if (build_matched) build_matched[r1 - 1] = 1;
-            ++pos;
+        // multi-match: nmb > 0 implies a non-empty first slot
+        if (fk[b] == k[b]) {
+          long long r1 = fr[b] & SLOT_ROW;
+          if (pos < out_capacity) {
+            out_build[pos] = (int32_t)(r1 - 1);
+            out_probe[pos] = prow;
           }
-          if (!(cur.row1 & SLOT_CHAIN)) break;
+          if (build_matched) build_matched[r1 - 1] = 1;
+          ++pos;
+        }
+        if (fr[b] & SLOT_CHAIN) {
+          uint64_t sl = s[b];
+          while (true) {
+            sl = (sl + 1) & mask;
+            longlong2 v = slots2[sl];
+            if (v.y == 0) break;
+            if (v.x == k[b]) {
+              long long r1 = v.y & SLOT_ROW;
+              if (pos < out_capacity) {
+                out_build[pos] = (int32_t)(r1 - 1);
+                out_probe[pos] = prow;
+              }
+              if (build_matched) build_matched[r1 - 1] = 1;
+              ++pos;
+            }
+            if (!(v.y & SLOT_CHAIN)) break;
+          }
+        }
+      }
+    }
+  }
+  if (!FILL) {
+    count_local = wave_sum(count_local);
+    if (lane == 0 && count_local)
+      atomicAdd((unsigned long long*)counter, (unsigned long long)count_local);
+  }
+}
+
+// ---------------------------------------------------------------------------
+// narrow table: 8-byte slots for keys whose range fits 32 bits (INT32/DATE32
+// columns, packed multi-key tuples, int64 surrogate keys of a dense range).
+//   word = (key - kmin) | (row + 1) << 32 | chain << 63;   0 = empty
+// One CAS 0 -> word claims the slot and publishes key and row together, so an
+// insert is one memory-side transaction instead of a CAS plus a scattered
+// key store, and the table is half the bytes at the same load. The slot index
+// still comes from the hash of the ORIGINAL key (part_hist / part_scatter
+// prefixes line up with table windows exactly as for the wide table).
+// K is the key column's element type: int columns are read in place.
+// ---------------------------------------------------------------------------
+constexpr unsigned long long NSLOT_CHAIN = 1ull << 63;
+constexpr uint32_t NSLOT_ROW = 0x7fffffffu;  // of the word's high half
+
+template <typename K>
+__global__ void join_build_n32_kernel(const K* __restrict__ keys,
+                                      const uint8_t* __restrict__ valid,
+                                      int64_t nrows,
+                                      unsigned long long* __restrict__ slots,
+                                      uint64_t mask, long long kmin) {
+  int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  int64_t nthreads = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t base = tid * PIPE; base < nrows; base += nthreads * PIPE) {
+    unsigned long long w[PIPE];
+    uint64_t s[PIPE];
+    unsigned long long prev[PIPE];
+#pragma unroll
+    for (int b = 0; b < PIPE; ++b) {
+      int64_t row = base + b;
+      bool act = row < nrows && is_valid(valid, row);
+      long long k = act ? (long long)keys[row] : 0;
+      // the host guarantees key - kmin < 2^32 for every valid build row
+      w[b] = act ? ((uint64_t)(uint32_t)((uint64_t)k - (uint64_t)kmin) |
+                    (uint64_t)(row + 1) << 32)
+                 : 0ull;
+      s[b] = act ? slot_of(i64_hash(k), mask) : 0;
+    }
+    // first-slot claims back-to-back; inactive lanes CAS 0->0 on slot 0
+#pragma unroll
+    for (int b = 0; b < PIPE; ++b) prev[b] = atomicCAS(&slots[s[b]], 0ull, w[b]);
+#pragma unroll
+    for (int b = 0; b < PIPE; ++b) {
+      if (w[b] == 0 || prev[b] == 0) continue;
+      // mark the displaced-over slots so probes know the chain continues
+      atomicOr(&slots[s[b]], NSLOT_CHAIN);
+      uint64_t sl = (s[b] + 1) & mask;
+      while (atomicCAS(&slots[sl], 0ull, w[b]) != 0) {
+        atomicOr(&slots[sl], NSLOT_CHAIN);
+        sl = (sl + 1) & mask;
+      }
+    }
+  }
+}
+
+// Same contract as join_probe_i64_kernel. A lane keeps only the 32-bit key
+// offset and the fetched word per row; the slot index of a row whose chain
+// continues is recomputed from kmin + offset on that (rare) path, which keeps
+// the batch state small enough for a fifth wave per SIMD.
+template <typename K, bool FILL, bool HAS_VALID>
+__global__ void join_probe_n32_kernel(
+    const K* __restrict__ probe, const uint8_t* __restrict__ pvalid,
+    int64_t nprobe, const unsigned long long* __restrict__ slots,
+    uint64_t mask, long long kmin, uint64_t* __restrict__ counter,
+    int32_t* __restrict__ out_build, int64_t* __restrict__ out_probe,
+    int64_t out_capacity, uint8_t* __restrict__ build_matched,
+    const int32_t* __restrict__ idxmap) {
+  static_assert(PIPE == 8, "one validity byte per batch");
+  int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  int64_t nthreads = (int64_t)gridDim.x * blockDim.x;
+  int lane = threadIdx.x & (WAVE - 1);
+  uint64_t count_local = 0;
+  int64_t nbatch = (nprobe + (int64_t)PIPE - 1) / PIPE;
+  // pad so every lane of a wave runs the same iterations (wave shuffles)
+  int64_t nbatch_pad = (nbatch + WAVE - 1) & ~(int64_t)(WAVE - 1);
+  for (int64_t batch = tid; batch < nbatch_pad; batch += nthreads) {
+    bool batch_ok = batch < nbatch;
+    int64_t base = batch_ok ? batch * PIPE : 0;
+    uint32_t vbits = (1u << PIPE) - 1u;
+    if (HAS_VALID) vbits = pvalid[base >> 3];
+    if (base + PIPE > nprobe) {
+      int64_t tail = nprobe - base;
+      vbits &= (uint32_t)((1u << (tail < 0 ? 0 : tail)) - 1u);
+    }
+    if (!batch_ok) vbits = 0;
+    uint32_t off[PIPE];
+    unsigned long long fw[PIPE];
+    {
+      uint64_t s[PIPE];
+#pragma unroll
+      for (int b = 0; b < PIPE; ++b) {
+        int64_t row = base + b;
+        long long k = (long long)probe[row < nprobe ? row : 0];  // clamped
+        s[b] = slot_of(i64_hash(k), mask);
+        uint64_t o = (uint64_t)k - (uint64_t)kmin;
+        off[b] = (uint32_t)o;
+        // an offset past 32 bits can never match; it must not alias
+        if (o >> 32) vbits &= ~(1u << b);
+      }
+#pragma unroll
+      for (int b = 0; b < PIPE; ++b) fw[b] = slots[s[b]];
+    }
+    uint32_t nm = 0;
+    uint32_t nmb[PIPE];
+    uint32_t hit1[PIPE];  // row + 1 of the first match
+#pragma unroll
+    for (int b = 0; b < PIPE; ++b) {
+      nmb[b] = 0;
+      hit1[b] = 0;
+      // word != 0 first: an empty slot must not match the key at offset 0
+      if (!((vbits >> b) & 1) || fw[b] == 0) continue;
+      if ((uint32_t)fw[b] == off[b]) {
+        hit1[b] = (uint32_t)(fw[b] >> 32) & NSLOT_ROW;
+        nmb[b] = 1;
+      }
+      if (fw[b] & NSLOT_CHAIN) {
+        uint64_t sl = slot_of(
+            i64_hash((long long)((uint64_t)kmin + (uint64_t)off[b])), mask);
+        while (true) {
           sl = (sl + 1) & mask;
-          cur = slots[sl];
+          unsigned long long w = slots[sl];
+          if (w == 0) break;
+          if ((uint32_t)w == off[b]) {
+            if (nmb[b] == 0) hit1[b] = (uint32_t)(w >> 32) & NSLOT_ROW;
+            ++nmb[b];
+          }
+          if (!(w & NSLOT_CHAIN)) break;  // chain ends here
+        }
+      }
+      nm += nmb[b];
+    }
+    if (!FILL) {
+      count_local += nm;
+      continue;
+    }
+    // emit: one atomic per wave; single-match rows write straight from the
+    // carried register, only multi-match rows rescan (cache-warm)
+    uint32_t incl = wave_prefix_incl(nm);
+    uint32_t total = __shfl(incl, WAVE - 1, WAVE);
+    uint64_t wave_base = 0;
+    if (lane == WAVE - 1 && total)
+      wave_base = atomicAdd((unsigned long long*)counter, (unsigned long long)total);
+    wave_base = __shfl(wave_base, WAVE - 1, WAVE);
+    int64_t pos = (int64_t)(wave_base + incl - nm);
+    if (nm) {
+#pragma unroll
+      for (int b = 0; b < PIPE; ++b) {
+        if (nmb[b] == 0) continue;
+        int64_t prow = idxmap ? (int64_t)idxmap[base + b] : base + b;
+        if (nmb[b] == 1) {
+          if (pos < out_capacity) {
+            out_build[pos] = (int32_t)(hit1[b] - 1);
+            out_probe[pos] = prow;
+          }
+          // matched flags are valid even when the pair output overflows
+          if (build_matched) build_matched[hit1[b] - 1] = 1;
+          ++pos;
+          continue;
+        }
+        // multi-match: nmb > 0 implies a non-empty first slot
+        if ((uint32_t)fw[b] == off[b]) {
+          uint32_t r1 = (uint32_t)(fw[b] >> 32) & NSLOT_ROW;
+          if (pos < out_capacity) {
+            out_build[pos] = (int32_t)(r1 - 1);
+            out_probe[pos] = prow;
+          }
+          if (build_matched) build_matched[r1 - 1] = 1;
+          ++pos;
+        }
+        if (fw[b] & NSLOT_CHAIN) {
+          uint64_t sl = slot_of(
+              i64_hash((long long)((uint64_t)kmin + (uint64_t)off[b])), mask);
+          while (true) {
+            sl = (sl + 1) & mask;
+            unsigned long long w = slots[sl];
+            if (w == 0) break;
+            if ((uint32_t)w == off[b]) {
+              uint32_t r1 = (uint32_t)(w >> 32) & NSLOT_ROW;
+              if (pos < out_capacity) {
+                out_build[pos] = (int32_t)(r1 - 1);
+                out_probe[pos] = prow;
+              }
+              if (build_matched) build_matched[r1 - 1] = 1;
+              ++pos;
+            }
+            if (!(w & NSLOT_CHAIN)) break;
+          }
         }
       }
     }
@@ -652,6 +880,74 @@ void srj_join_probe_i64(const long long* probe, const uint8_t* pvalid,
           probe, pvalid, nprobe, sl, mask, counter, nullptr, nullptr, 0,
           nullptr, nullptr);
   }
+}
+
+// key_i32 != 0: keys are a 4-byte int column read in place, else int64
+void srj_join_build_n32(const void* keys, int32_t key_i32, const uint8_t* valid,
+                        int64_t nrows, void* slots, int64_t capacity,
+                        long long kmin, hipStream_t stream) {
+  int64_t g = grid_1d((nrows + PIPE - 1) / PIPE);
+  auto* sl = reinterpret_cast<unsigned long long*>(slots);
+  uint64_t mask = (uint64_t)(capacity - 1);
+  if (key_i32)
+    join_build_n32_kernel<int><<<g, DEFAULT_BLOCK, 0, stream>>>(
+        reinterpret_cast<const int*>(keys), valid, nrows, sl, mask, kmin);
+  else
+    join_build_n32_kernel<long long><<<g, DEFAULT_BLOCK, 0, stream>>>(
+        reinterpret_cast<const long long*>(keys), valid, nrows, sl, mask, kmin);
+}
+
+}  // extern "C"
+
+template <typename K>
+static void launch_probe_n32(const K* probe, const uint8_t* pvalid,
+                             int64_t nprobe, const unsigned long long* sl,
+                             uint64_t mask, long long kmin, uint64_t* counter,
+                             int32_t* out_build, int64_t* out_probe,
+                             int64_t out_capacity, uint8_t* build_matched,
+                             int32_t fill, const int32_t* idxmap,
+                             hipStream_t stream) {
+  int64_t g = grid_1d((nprobe + PIPE - 1) / PIPE);
+  if (fill) {
+    if (pvalid)
+      join_probe_n32_kernel<K, true, true><<<g, DEFAULT_BLOCK, 0, stream>>>(
+          probe, pvalid, nprobe, sl, mask, kmin, counter, out_build, out_probe,
+          out_capacity, build_matched, idxmap);
+    else
+      join_probe_n32_kernel<K, true, false><<<g, DEFAULT_BLOCK, 0, stream>>>(
+          probe, pvalid, nprobe, sl, mask, kmin, counter, out_build, out_probe,
+          out_capacity, build_matched, idxmap);
+  } else {
+    if (pvalid)
+      join_probe_n32_kernel<K, false, true><<<g, DEFAULT_BLOCK, 0, stream>>>(
+          probe, pvalid, nprobe, sl, mask, kmin, counter, nullptr, nullptr, 0,
+          nullptr, nullptr);
+    else
+      join_probe_n32_kernel<K, false, false><<<g, DEFAULT_BLOCK, 0, stream>>>(
+          probe, pvalid, nprobe, sl, mask, kmin, counter, nullptr, nullptr, 0,
+          nullptr, nullptr);
+  }
+}
+
+extern "C" {
+
+void srj_join_probe_n32(const void* probe, int32_t key_i32,
+                        const uint8_t* pvalid, int64_t nprobe, const void* slots,
+                        int64_t capacity, long long kmin, uint64_t* counter,
+                        int32_t* out_build, int64_t* out_probe,
+                        int64_t out_capacity, uint8_t* build_matched,
+                        int32_t fill, const int32_t* idxmap,
+                        hipStream_t stream) {
+  auto* sl = reinterpret_cast<const unsigned long long*>(slots);
+  uint64_t mask = (uint64_t)(capacity - 1);
+  if (key_i32)
+    launch_probe_n32(reinterpret_cast<const int*>(probe), pvalid, nprobe, sl,
+                     mask, kmin, counter, out_build, out_probe, out_capacity,
+                     build_matched, fill, idxmap, stream);
+  else
+    launch_probe_n32(reinterpret_cast<const long long*>(probe), pvalid, nprobe,
+                     sl, mask, kmin, counter, out_build, out_probe,
+                     out_capacity, build_matched, fill, idxmap, stream);
 }
 
 void srj_groupby_i64_lds(const long long* keys, int64_t nrows, void* slots,
