@@ -190,6 +190,91 @@ def sort_order_bench(n, iters, dev, g):
             print(json.dumps(rec), flush=True)
 
 
+def parent_window(fn, perm, bnd, change, vdata, vvalid):
+    """The expression NDS Window ran per function before the native window
+    op, from the sort order `perm` and the partition flags `bnd` on (`change`:
+    the peer flags, for rank)."""
+    n = perm.numel()
+    dev = perm.device
+    inv = torch.empty_like(perm)
+    inv[perm] = torch.arange(n, dtype=torch.int64, device=dev)
+    seg = torch.cumsum(bnd.to(torch.int64), 0) - 1
+    nseg = int(seg[-1].item()) + 1
+    seg_start = torch.zeros(nseg, dtype=torch.int64, device=dev)
+    seg_start.scatter_(0, seg[bnd], torch.nonzero(
+        bnd, as_tuple=False).view(-1))
+    pos = torch.arange(n, dtype=torch.int64, device=dev) - \
+        seg_start[seg]
+    if fn == "sum":
+        data = vdata[perm].to(torch.float64)
+        vm = (vvalid[perm] if vvalid is not None
+              else torch.ones(n, dtype=torch.bool, device=dev))
+        acc = torch.zeros(nseg, dtype=torch.float64, device=dev)
+        acc.index_add_(0, seg, torch.where(vm, data,
+                                           torch.zeros_like(data)))
+        res_sorted = acc[seg]
+    elif fn == "cumsum":
+        data = vdata[perm].to(torch.float64)
+        vm = (vvalid[perm] if vvalid is not None
+              else torch.ones(n, dtype=torch.bool, device=dev))
+        data = torch.where(vm, data, torch.zeros_like(data))
+        cs = torch.cumsum(data, 0)
+        base = torch.zeros(nseg, dtype=torch.float64, device=dev)
+        starts = torch.nonzero(bnd, as_tuple=False).view(-1)
+        base[1:] = cs[starts[1:] - 1]
+        res_sorted = cs - base[seg]
+    else:  # rank (`pos`, above, is computed for every function)
+        idx = torch.arange(n, dtype=torch.int64, device=dev)
+        last_change = torch.cummax(
+            torch.where(change, idx,
+                        torch.full_like(idx, -1)), 0)[0]
+        res_sorted = last_change - seg_start[seg] + 1
+    return res_sorted[inv]
+
+
+def window_bench(n, dev, g):
+    """window_tensors against parent_window on rank over 2 partition keys
+    plus 1 order key, a partition sum and a running sum. Both sides start
+    from the same sort order and boundary flags; the sort is not timed."""
+    from spark_rapids_jni_amd.ops.sort import (key_change_flags,
+                                               sort_order_tensors)
+    from spark_rapids_jni_amd.ops.window import window_tensors
+    ri = lambda hi: torch.randint(0, hi, (n,), device=dev, generator=g)
+    # about 8 rows per partition, ties in the order key
+    side = max(2, int((n / 8) ** 0.5))
+    k1, k2, ok = ri(side), ri(side), ri(4)
+    vdata = torch.randint(-400, 400, (n,), device=dev,
+                          generator=g).to(torch.float64) / 4
+    vvalid = torch.rand(n, device=dev, generator=g) < 0.9
+    perm = sort_order_tensors([k1, k2, ok])
+    bnd = key_change_flags([k1, k2], perm)
+    change = key_change_flags([k1, k2, ok], perm)
+    cases = {
+        "rank": ([("rank", None, None, "rows")], "rank"),
+        "partition_sum": ([("sum", vdata, vvalid, "partition")], "sum"),
+        "cumsum": ([("sum", vdata, vvalid, "rows")], "cumsum"),
+    }
+    reps = 20
+    inner = 20 if n <= 2**16 else 1
+    for name, (funcs, fn) in cases.items():
+        new = lambda: window_tensors(perm, bnd, funcs, change)[0][0]
+        old = lambda: parent_window(fn, perm, bnd, change, vdata, vvalid)
+        # quarter-integers: every order of summation is exact
+        assert torch.equal(new().to(torch.float64),
+                           old().to(torch.float64)), name
+        new_s, old_s = ab_time(new, old, inner, repeats=reps)
+        launches = {"hip": count_launches(new),
+                    "torch_parent": count_launches(old)}
+        for path, xs in (("hip", new_s), ("torch_parent", old_s)):
+            xs = sorted(xs)
+            print(json.dumps({
+                "bench": "window_" + name, "path": path, "rows": n,
+                "repeats": reps, "launches": launches[path],
+                "ms": round(xs[len(xs) // 2] * 1e3, 4),
+                "ms_min": round(xs[0] * 1e3, 4),
+                "ms_max": round(xs[-1] * 1e3, 4)}), flush=True)
+
+
 def join_narrow_bench(nb, npr, iters, dev, g):
     """Narrow (8-byte slot) against wide (16-byte slot) join table on the same
     dense int64 keys, build and probe timed separately and alternating. The
@@ -259,10 +344,16 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=2**24)
     ap.add_argument("--iters", type=int, default=5)
-    ap.add_argument("--only", choices=["sort_order", "join_narrow"],
+    ap.add_argument("--only", choices=["sort_order", "join_narrow", "window"],
                     default=None,
                     help="run just this group")
     args = ap.parse_args()
+    if args.only == "window":
+        g = torch.Generator(device="cuda")
+        g.manual_seed(7)
+        for wn in (2**11, 2**16, 2**20, 2**24):
+            window_bench(wn, "cuda", g)
+        return
     if args.only == "sort_order":
         g = torch.Generator(device="cuda")
         g.manual_seed(7)

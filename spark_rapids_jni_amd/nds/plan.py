@@ -477,6 +477,22 @@ class CpuBackend:
 NATIVE_SORT_ANY_KEYS_ROWS = 2048
 TORCH_SORT_MAX_KEYS = 2
 
+# GPU window routing: ops/window.py measured faster than the torch expression
+# of _exec_window at every size and function (the window table in
+# docs/PERF.md), so every CUDA frame takes it. NDS function -> (function,
+# frame) of ops/window.py; min and max under an order stay whole-partition,
+# as on the CPU path (the known deviation noted in docs/PERF.md).
+_WINDOW_FUNCS = {
+    "sum": ("sum", "partition"), "avg": ("avg", "partition"),
+    "min": ("min", "partition"), "max": ("max", "partition"),
+    "cumsum": ("sum", "rows"), "rank": ("rank", "rows"),
+    "dense_rank": ("dense_rank", "rows"),
+    "row_number": ("row_number", "rows"),
+}
+# what the torch expression leaves where a frame holds no valid value
+_WINDOW_NULL_FILL = {"sum": 0.0, "cumsum": 0.0, "avg": 0.0,
+                     "min": float("inf"), "max": float("-inf")}
+
 
 class Engine:
     def __init__(self, catalog, device="cuda", world: int = 1, rank: int = 0,
@@ -893,6 +909,8 @@ class Engine:
                 out[spec[0]] = Val(torch.zeros(0, dtype=torch.int64,
                                                device=dev))
             return Frame(out, 0)
+        if self.device.type == "cuda":
+            return self._exec_window_native(p, f)
         out = dict(f.cols)
         for spec in p.funcs:
             name, fn, arg = spec[0], spec[1], spec[2]
@@ -1004,6 +1022,63 @@ class Engine:
                 out[name] = Val(res_sorted[inv])
             else:
                 raise ValueError(fn)
+        return Frame(out, n, f.sharded)
+
+    def _exec_window_native(self, p: Window, f: Frame) -> Frame:
+        """Window on a CUDA frame through ops/window.py: specs that share an
+        order share one sort, one pair of boundary-flag calls and one
+        window_tensors call, and nothing is read back to the host. Results
+        keep the conventions of the torch expression in _exec_window:
+        float64 aggregates without validity, nulls as its fills."""
+        from ..ops.window import window_tensors
+        n = f.nrows
+        dev = self.device
+        groups: Dict[tuple, List[tuple]] = {}
+        for spec in p.funcs:
+            if spec[1] not in _WINDOW_FUNCS:
+                raise ValueError(spec[1])
+            order = spec[3] if len(spec) > 3 else None
+            key = tuple((c, bool(asc)) for c, asc in order) if order else ()
+            groups.setdefault(key, []).append(spec)
+        as_f64: Dict[str, torch.Tensor] = {}
+        res: Dict[str, Val] = {}
+        for key, specs in groups.items():
+            # sort rows: partition keys asc, then order keys
+            sort_keys = [(k, True) for k in p.partition] + list(key)
+            if sort_keys:
+                perm = self._argsort(f, sort_keys)
+            else:
+                perm = torch.arange(n, dtype=torch.int64, device=dev)
+            if p.partition:
+                part = self._key_change(f, p.partition, perm)
+            else:  # one partition: the op makes position 0 its head
+                part = torch.zeros(n, dtype=torch.bool, device=dev)
+            peer = None
+            funcs = []
+            for spec in specs:
+                fn, arg = spec[1], spec[2]
+                wfn, frame = _WINDOW_FUNCS[fn]
+                if fn in ("rank", "dense_rank", "row_number"):
+                    assert key, f"{fn} needs an order"
+                    if peer is None:
+                        peer = self._key_change(
+                            f, list(p.partition) + [c for c, _a in key], perm)
+                    funcs.append((wfn, None, None, frame))
+                else:
+                    v = f.cols[arg]
+                    if arg not in as_f64:
+                        as_f64[arg] = v.data.to(torch.float64)
+                    funcs.append((wfn, as_f64[arg], v.valid, frame))
+            for spec, (data, valid) in zip(
+                    specs, window_tensors(perm, part, funcs, peer)):
+                fill = _WINDOW_NULL_FILL.get(spec[1], 0.0)
+                if valid is not None and fill != 0.0:
+                    data = torch.where(valid, data,
+                                       torch.full_like(data, fill))
+                res[spec[0]] = Val(data)
+        out = dict(f.cols)
+        for spec in p.funcs:
+            out[spec[0]] = res[spec[0]]
         return Frame(out, n, f.sharded)
 
     @staticmethod

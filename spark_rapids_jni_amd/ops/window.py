@@ -1,0 +1,400 @@
+"""Window functions over a sorted order (Spark WindowExec's GPU half; cudf
+grouped scans and rolling aggregations over unbounded frames).
+
+`window_tensors` takes the permutation that sorts the rows by (partition keys,
+order keys) and the partition / peer boundary flags of the sorted rows - what
+`sort_order_tensors` and `key_change_flags` give - and evaluates any number of
+window functions in one call of the segmented-scan kernels of
+src/gpu/window.hip. Values are read in place through the permutation and
+results land in original row order. `window_columns` is the same on Tables.
+
+Functions: row_number, rank, dense_rank, count, sum, min, max, avg. Frames of
+the five aggregates: "partition" (the whole partition), "rows" (unbounded
+preceding to the current row) and "range" (unbounded preceding through the
+current row's last peer: Spark's default frame under an ORDER BY). Ranking
+functions ignore the frame.
+
+Semantics (Spark, non-ANSI): aggregates skip nulls; count is int64 and never
+null; sum is int64 (wrapping) for integer and bool input and float64 for float
+input; min and max keep the input dtype, with NaN greater than every value;
+avg accumulates and divides in float64; sum, min, max and avg are null (data
+zero) where the frame holds no valid value. Ranking results are int64.
+
+CPU tensors take an equivalent torch expression; CUDA tensors always take the
+native kernels: no host sync (the op runs under stream capture), no atomics,
+and the same input gives bit-identical output on every run.
+"""
+from typing import List, Optional, Sequence, Tuple
+
+import torch
+
+from .. import _native
+from ..columnar import Column, DType, Table, validity_to_bool
+
+# mirrors of src/gpu/window.hpp
+WINDOW_MAX_FUNCS = 8
+SMALL_ROWS = 2048
+TILE_ROWS = 2048
+CARRY_CHUNK = 1024  # tile carries per round of the carry scan
+
+_FUNCS = {"row_number": 0, "rank": 1, "dense_rank": 2, "count": 3, "sum": 4,
+          "min": 5, "max": 6, "avg": 7}
+_RANKING = ("row_number", "rank", "dense_rank")
+_FRAMES = {"partition": 0, "rows": 1, "range": 2}
+_WK_NONE, _WK_BOOL, _WK_SINT, _WK_F32, _WK_F64 = range(5)
+_VALUE_KINDS = {
+    torch.bool: _WK_BOOL, torch.int8: _WK_SINT, torch.int16: _WK_SINT,
+    torch.int32: _WK_SINT, torch.int64: _WK_SINT, torch.float32: _WK_F32,
+    torch.float64: _WK_F64,
+}
+_BYTE_DTYPES = (torch.bool, torch.uint8, torch.int8)
+
+
+def window_work_bytes(m: int, nfuncs: int) -> int:
+    """Bytes of scratch one kernel call over m rows and nfuncs functions
+    takes (zero on the one-workgroup path)."""
+    return _native.gpu().window_work_bytes(m, nfuncs)
+
+
+class _Func:
+    __slots__ = ("fn", "values", "valid", "frame")
+
+    def __init__(self, fn, values, valid, frame):
+        self.fn, self.values, self.valid, self.frame = fn, values, valid, frame
+
+    def out_dtype(self):
+        if self.fn in _RANKING or self.fn == "count":
+            return torch.int64
+        if self.fn == "avg":
+            return torch.float64
+        if self.fn == "sum":
+            return (torch.float64 if self.values.dtype.is_floating_point
+                    else torch.int64)
+        return self.values.dtype
+
+    def nullable(self):
+        return (self.fn not in _RANKING and self.fn != "count"
+                and self.valid is not None)
+
+
+def _check_flags(t, what, m, dev):
+    if not isinstance(t, torch.Tensor) or t.dtype not in _BYTE_DTYPES:
+        raise TypeError(f"{what} must be a bool, uint8 or int8 tensor")
+    if t.dim() != 1 or t.numel() != m:
+        raise ValueError(f"{what} must be 1-D with {m} rows")
+    if t.device != dev:
+        raise ValueError(f"{what} and perm are on different devices")
+    return t.contiguous()
+
+
+def _check_funcs(funcs, m, dev, have_peer) -> List[_Func]:
+    out = []
+    for i, spec in enumerate(funcs):
+        if len(spec) != 4:
+            raise ValueError(f"funcs[{i}] must be (fn, values, valid, frame)")
+        fn, values, valid, frame = spec
+        if fn not in _FUNCS:
+            raise ValueError(f"funcs[{i}]: unknown function {fn!r}")
+        if fn in _RANKING:
+            if not have_peer:
+                raise ValueError(f"funcs[{i}]: {fn} needs peer_flags")
+            if values is not None or valid is not None:
+                raise ValueError(f"funcs[{i}]: {fn} takes no values")
+            out.append(_Func(fn, None, None, "rows"))
+            continue
+        if frame not in _FRAMES:
+            raise ValueError(f"funcs[{i}]: unknown frame {frame!r}")
+        if values is None:
+            if fn != "count":
+                raise ValueError(f"funcs[{i}]: {fn} needs values")
+        else:
+            if not isinstance(values, torch.Tensor):
+                raise TypeError(f"funcs[{i}]: values must be a torch.Tensor")
+            if values.dtype not in _VALUE_KINDS:
+                raise TypeError(f"funcs[{i}]: unsupported dtype "
+                                f"{values.dtype}")
+            if values.dim() != 1:
+                raise ValueError(f"funcs[{i}]: values must be 1-D, got shape "
+                                 f"{tuple(values.shape)}")
+            if values.numel() != m:
+                raise ValueError(f"funcs[{i}]: values has {values.numel()} "
+                                 f"rows but perm has {m}")
+            if values.device != dev:
+                raise ValueError(f"funcs[{i}]: values and perm are on "
+                                 "different devices")
+        if valid is not None:
+            if not isinstance(valid, torch.Tensor) or \
+                    valid.dtype not in _BYTE_DTYPES:
+                raise TypeError(f"funcs[{i}]: valid must be a bool, uint8 or "
+                                "int8 tensor")
+            if valid.dim() != 1 or valid.numel() != m:
+                raise ValueError(f"funcs[{i}]: valid must be 1-D with {m} "
+                                 "rows")
+            if valid.device != dev:
+                raise ValueError(f"funcs[{i}]: valid and perm are on "
+                                 "different devices")
+            valid = valid.contiguous()
+        out.append(_Func(fn, values, valid, frame))
+    return out
+
+
+# ---------------------------------------------------------------------------
+# CPU twin
+# ---------------------------------------------------------------------------
+
+def _merge(op, ca, aa, cb, ab):
+    """Accumulator of `a` (left) combined with `b`; counts decide validity
+    for min and max, sums hold zero under nulls."""
+    if op == "sum":
+        return aa + ab
+    if op == "none":
+        return ab
+    if op == "maxidx":
+        return torch.maximum(aa, ab)
+    if aa.dtype.is_floating_point:
+        # NaN greatest: maximum propagates NaN, fmin drops it
+        both = torch.maximum(aa, ab) if op == "max" else torch.fmin(aa, ab)
+    else:
+        both = torch.maximum(aa, ab) if op == "max" else torch.minimum(aa, ab)
+    return torch.where(ca == 0, ab, torch.where(cb == 0, aa, both))
+
+
+def _seg_scan_cpu(head, cnt, acc, op):
+    """Inclusive segmented scan by doubling: the torch twin of the kernels'
+    scan (same operator, another association)."""
+    m = head.numel()
+    flag = head.clone()
+    d = 1
+    while d < m:
+        take = ~flag[d:]
+        zero = torch.zeros_like(cnt[:-d])
+        merged = _merge(op, cnt[:-d], acc[:-d], cnt[d:], acc[d:])
+        acc = torch.cat([acc[:d], torch.where(take, merged, acc[d:])])
+        cnt = torch.cat([cnt[:d], cnt[d:] + torch.where(take, cnt[:-d],
+                                                        zero)])
+        flag = torch.cat([flag[:d], flag[d:] | flag[:-d]])
+        d *= 2
+    return cnt, acc
+
+
+def _frame_last(head):
+    """Last sorted position of the segment each position lies in."""
+    m = head.numel()
+    idx = torch.arange(m, dtype=torch.int64, device=head.device)
+    nxt = torch.where(head, idx, torch.full_like(idx, m))
+    nxt = torch.flip(torch.cummin(torch.flip(nxt, [0]), 0)[0], [0])
+    return torch.cat([nxt[1:], nxt.new_full((1,), m)]) - 1
+
+
+def _window_cpu(perm, part, peer, fs: List[_Func]):
+    m = perm.numel()
+    dev = perm.device
+    idx = torch.arange(m, dtype=torch.int64, device=dev)
+    ends = {"rows": idx, "partition": _frame_last(part),
+            "range": _frame_last(peer)}
+    ones = torch.ones(m, dtype=torch.int64, device=dev)
+    results = []
+    for f in fs:
+        if f.fn in _RANKING:
+            if f.fn == "dense_rank":
+                cnt, _ = _seg_scan_cpu(part, peer.to(torch.int64), ones,
+                                       "none")
+                res = cnt
+            else:
+                cnt, last_peer = _seg_scan_cpu(
+                    part, ones, torch.where(peer, idx, -ones), "maxidx")
+                res = cnt if f.fn == "row_number" else cnt - idx + last_peer
+            data = torch.empty_like(res)
+            data[perm] = res
+            results.append((data, None))
+            continue
+        valid = (f.valid[perm] != 0 if f.valid is not None
+                 else torch.ones(m, dtype=torch.bool, device=dev))
+        cnt = valid.to(torch.int64)
+        if f.fn == "count":
+            acc, op = ones, "none"
+        else:
+            v = f.values[perm]
+            if f.fn == "avg" or v.dtype.is_floating_point:
+                acc = v.to(torch.float64)
+            else:
+                acc = v.to(torch.int64)
+            op = "sum" if f.fn in ("sum", "avg") else f.fn
+            acc = torch.where(valid, acc, torch.zeros_like(acc))
+        cnt, acc = _seg_scan_cpu(part, cnt, acc, op)
+        e = ends[f.frame]
+        cnt, acc = cnt[e], acc[e]
+        has = cnt > 0
+        if f.fn == "count":
+            res = cnt
+        elif f.fn == "avg":
+            res = acc / cnt.clamp(min=1).to(torch.float64)
+        else:
+            res = acc
+            res = torch.where(has, res, torch.zeros_like(res))
+        res = res.to(f.out_dtype())
+        data = torch.empty_like(res)
+        data[perm] = res
+        ov = None
+        if f.nullable():
+            ov = torch.empty(m, dtype=torch.bool, device=dev)
+            ov[perm] = has
+        results.append((data, ov))
+    return results
+
+
+# ---------------------------------------------------------------------------
+# native path
+# ---------------------------------------------------------------------------
+
+def _window_gpu(perm, part, peer, fs: List[_Func], have_peer):
+    g = _native.gpu()
+    m = perm.numel()
+    dev = perm.device
+    stream = _native.current_stream()
+    results = []
+    for lo in range(0, len(fs), WINDOW_MAX_FUNCS):
+        chunk = fs[lo:lo + WINDOW_MAX_FUNCS]
+        descs = []
+        for f in chunk:
+            data = torch.empty(m, dtype=f.out_dtype(), device=dev)
+            ov = (torch.empty(m, dtype=torch.bool, device=dev)
+                  if f.nullable() else None)
+            if f.values is None:
+                kind, width, stride, vptr = _WK_NONE, 1, 1, 0
+            else:
+                kind = _VALUE_KINDS[f.values.dtype]
+                width = f.values.element_size()
+                stride = f.values.stride(0) if m > 1 else 1
+                if stride < 1:
+                    f.values = f.values.contiguous()
+                    stride = 1
+                vptr = f.values.data_ptr()
+            descs.append((_FUNCS[f.fn], _FRAMES[f.frame], kind, width, stride,
+                          vptr,
+                          f.valid.data_ptr() if f.valid is not None else 0,
+                          data.data_ptr(),
+                          ov.data_ptr() if ov is not None else 0))
+            results.append((data, ov))
+        nbytes = g.window_work_bytes(m, len(chunk))
+        work = torch.empty(nbytes // 8, dtype=torch.int64, device=dev) \
+            if nbytes else None
+        g.window(descs, perm.data_ptr(), part.data_ptr(),
+                 peer.data_ptr() if have_peer else 0, m,
+                 work.data_ptr() if work is not None else 0, stream)
+    return results
+
+
+def window_tensors(perm: torch.Tensor, part_flags: torch.Tensor,
+                   funcs: Sequence[Tuple],
+                   peer_flags: Optional[torch.Tensor] = None
+                   ) -> List[Tuple[torch.Tensor, Optional[torch.Tensor]]]:
+    """Window functions over the sorted order `perm`.
+
+    `part_flags[i]` / `peer_flags[i]` are nonzero where sorted position i
+    starts a partition / a peer group (position 0 always does, and a
+    partition head is a peer head, whatever the flags say). Without
+    `peer_flags` every row is its own peer group. `funcs` is a list of
+    `(fn, values, valid, frame)`: `values` and `valid` (a byte per row, zero
+    = null) are indexed by original row and are None for the ranking
+    functions and count(*). Returns one `(data, valid)` per function in
+    original row order; `valid` is a bool tensor, or None for count, the
+    ranking functions and inputs without validity.
+    """
+    if not isinstance(perm, torch.Tensor) or perm.dtype != torch.int64:
+        raise TypeError("perm must be an int64 tensor")
+    if perm.dim() != 1:
+        raise ValueError(f"perm must be 1-D, got shape {tuple(perm.shape)}")
+    m = perm.numel()
+    dev = perm.device
+    part = _check_flags(part_flags, "part_flags", m, dev)
+    have_peer = peer_flags is not None
+    peer = _check_flags(peer_flags, "peer_flags", m, dev) if have_peer \
+        else None
+    fs = _check_funcs(list(funcs), m, dev, have_peer)
+    if m == 0:
+        return [(torch.empty(0, dtype=f.out_dtype(), device=dev),
+                 torch.empty(0, dtype=torch.bool, device=dev)
+                 if f.nullable() else None) for f in fs]
+    if not fs:
+        return []
+    perm = perm.contiguous()
+    if dev.type == "cuda":
+        return _window_gpu(perm, part, peer, fs, have_peer)
+    part = part != 0
+    part[0] = True
+    peer = (peer != 0) | part if have_peer else torch.ones_like(part)
+    return _window_cpu(perm, part, peer, fs)
+
+
+_VALUE_COLUMNS = (DType.BOOL8, DType.INT8, DType.INT16, DType.INT32,
+                  DType.INT64, DType.FLOAT32, DType.FLOAT64, DType.DATE32,
+                  DType.TIMESTAMP_US)
+_OUT_DTYPE = {torch.int8: DType.INT8, torch.int16: DType.INT16,
+              torch.int32: DType.INT32, torch.int64: DType.INT64,
+              torch.float32: DType.FLOAT32, torch.float64: DType.FLOAT64}
+
+
+def window_columns(partition_by: Optional[Table], order_by: Optional[Table],
+                   funcs, ascending: Optional[Sequence[bool]] = None,
+                   nulls_first: Optional[Sequence] = None) -> List[Column]:
+    """Window functions `funcs` = [(fn, Column or None, frame)] over the
+    partitions of `partition_by` (None, a Table cannot be empty: one
+    partition) ordered by
+    `order_by` (`ascending` / `nulls_first` as in `sort_order`). Partition
+    and order keys compare as the sort does: nulls equal each other, NaNs
+    equal, -0.0 == 0.0. Results are Columns in input row order."""
+    from .aggregate import _validity_from_bool
+    from .sort import _key_change_keys, _sort_order_keys, _table_keys
+    funcs = list(funcs)
+    pkeys = (_table_keys(partition_by, None, None)
+             if partition_by is not None else [])
+    okeys = (_table_keys(order_by, ascending, nulls_first)
+             if order_by is not None else [])
+    n = None
+    for t in (partition_by, order_by):
+        if t is not None:
+            if n is not None and t.num_rows != n:
+                raise ValueError(f"order_by has {t.num_rows} rows but "
+                                 f"partition_by has {n}")
+            n, dev = t.num_rows, t.device
+    for i, spec in enumerate(funcs):
+        if len(spec) != 3:
+            raise ValueError(f"funcs[{i}] must be (fn, column, frame)")
+        c = spec[1]
+        if c is not None:
+            if c.dtype not in _VALUE_COLUMNS:
+                raise NotImplementedError(
+                    f"window: {c.dtype.name} values are not supported")
+            if n is None:
+                n, dev = c.size, c.device
+            if c.size != n:
+                raise ValueError(f"funcs[{i}]: column has {c.size} rows but "
+                                 f"the keys have {n}")
+    if n is None:
+        raise ValueError("window_columns needs a key or a value column")
+    perm = _sort_order_keys(pkeys + okeys, n, torch.device(dev))
+    if pkeys and n:
+        part = _key_change_keys(pkeys, perm, n)
+    else:
+        part = torch.zeros(n, dtype=torch.bool, device=dev)
+    # no order: the rows of a partition are all peers
+    peer = _key_change_keys(pkeys + okeys, perm, n) if okeys and n else part
+    specs = []
+    for fn, c, frame in funcs:
+        if c is None:
+            specs.append((fn, None, None, frame))
+        else:
+            valid = (validity_to_bool(c.validity, c.size)
+                     if c.validity is not None else None)
+            specs.append((fn, c.data, valid, frame))
+    out = []
+    for (fn, c, _frame), (data, valid) in zip(
+            funcs, window_tensors(perm, part, specs, peer)):
+        if fn in ("min", "max"):
+            dt, scale = c.dtype, c.scale
+        else:
+            dt, scale = _OUT_DTYPE[data.dtype], 0
+        mask = _validity_from_bool(valid) if valid is not None else None
+        out.append(Column(dt, n, data, mask, scale=scale))
+    return out
