@@ -275,6 +275,62 @@ def window_bench(n, dev, g):
                 "ms_max": round(xs[-1] * 1e3, 4)}), flush=True)
 
 
+def expr_bench(n, dev, g):
+    """NDS eval_expr on the fused expression kernel against the same
+    eval_expr forced to its torch evaluator, alternating in one process:
+    a nullable filter predicate, a case_when product and a ratio with
+    coalesce. The compiled program is memoised, as in a query run."""
+    from spark_rapids_jni_amd.nds import expr as X
+    from spark_rapids_jni_amd.nds.expr import Val, case_when, coalesce, col
+    ri = lambda lo, hi: torch.randint(lo, hi, (n,), device=dev, generator=g,
+                                      dtype=torch.int32)
+    rf = lambda s: torch.rand(n, device=dev, generator=g,
+                              dtype=torch.float64) * s
+    rv = lambda p: torch.rand(n, device=dev, generator=g) < p
+    env = {"qty": Val(ri(0, 100), rv(0.9)), "sk": Val(ri(1, 2000)),
+           "year": Val(ri(1998, 2003), rv(0.95)),
+           "price": Val(rf(200), rv(0.9)), "cost": Val(rf(100)),
+           "disc": Val(rf(10), rv(0.5)), "zero": Val(ri(0, 3), rv(0.9))}
+    c = col
+    cases = {
+        "filter": (c("qty").between(10, 60) & c("sk").isin([3, 5, 7, 11, 13])
+                   | (c("year") == 2000) & (c("price") > 50.0)),
+        "case_product": case_when((c("year") == 1999,
+                                   c("qty") * c("price")), otherwise=0),
+        "ratio_coalesce": coalesce((c("price") - c("cost")) / c("zero"),
+                                   c("disc"), 0.0),
+    }
+
+    def run(e, force):
+        def fn():
+            X.FORCE_TORCH = force
+            try:
+                return X.eval_expr(e, env, n, dev)
+            finally:
+                X.FORCE_TORCH = False
+        return fn
+
+    reps = 20
+    inner = 20 if n <= 2**16 else 1
+    for name, e in cases.items():
+        new, old = run(e, False), run(e, True)
+        a, b = new(), old()
+        assert a.data.dtype == b.data.dtype, name
+        assert torch.equal(a.data, b.data), name  # no NaN in these shapes
+        assert (a.valid is None) == (b.valid is None), name
+        assert a.valid is None or torch.equal(a.valid, b.valid), name
+        new_s, old_s = ab_time(new, old, inner, repeats=reps)
+        launches = {"hip": count_launches(new), "torch": count_launches(old)}
+        for path, xs in (("hip", new_s), ("torch", old_s)):
+            xs = sorted(xs)
+            print(json.dumps({
+                "bench": "expr_" + name, "path": path, "rows": n,
+                "repeats": reps, "launches": launches[path],
+                "ms": round(xs[len(xs) // 2] * 1e3, 4),
+                "ms_min": round(xs[0] * 1e3, 4),
+                "ms_max": round(xs[-1] * 1e3, 4)}), flush=True)
+
+
 def join_narrow_bench(nb, npr, iters, dev, g):
     """Narrow (8-byte slot) against wide (16-byte slot) join table on the same
     dense int64 keys, build and probe timed separately and alternating. The
@@ -344,7 +400,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=2**24)
     ap.add_argument("--iters", type=int, default=5)
-    ap.add_argument("--only", choices=["sort_order", "join_narrow", "window"],
+    ap.add_argument("--only", choices=["sort_order", "join_narrow", "window",
+                                      "expr"],
                     default=None,
                     help="run just this group")
     args = ap.parse_args()
@@ -353,6 +410,12 @@ def main():
         g.manual_seed(7)
         for wn in (2**11, 2**16, 2**20, 2**24):
             window_bench(wn, "cuda", g)
+        return
+    if args.only == "expr":
+        g = torch.Generator(device="cuda")
+        g.manual_seed(7)
+        for en in (2**11, 2**16, 2**20, 2**24):
+            expr_bench(en, "cuda", g)
         return
     if args.only == "sort_order":
         g = torch.Generator(device="cuda")

@@ -20,7 +20,8 @@ from typing import Dict, List, Optional, Sequence, Tuple, Union as PyUnion
 
 import torch
 
-from .expr import Expr, Col, Lit, Val, eval_expr, _wrap
+from .expr import (Expr, Col, Lit, Val, ExprStats, eval_expr, eval_exprs,
+                   eval_keep, _wrap)
 
 
 # ---------------------------------------------------------------------------
@@ -506,6 +507,9 @@ class Engine:
                                    else CpuBackend())
         self.temps: Dict[str, Frame] = {}
         self._scan_cache: Dict[str, Frame] = {}
+        # CUDA expression route: kernel calls, and the fallbacks to the
+        # torch evaluator with their reasons
+        self.expr_stats = ExprStats()
 
     # -- public ------------------------------------------------------------
     def run(self, plan: Plan) -> Frame:
@@ -585,17 +589,29 @@ class Engine:
 
     def _exec_filter(self, p: Filter) -> Frame:
         f = self._exec(p.child)
+        if self.device.type == "cuda":
+            # one launch writes the keep byte
+            return f.mask(eval_keep(p.cond, f.cols, f.nrows, self.device,
+                                    self.expr_stats))
         v = eval_expr(p.cond, f.cols, f.nrows, self.device)
         m = v.data.bool()
         if v.valid is not None:
             m = m & v.valid
         return f.mask(m)
 
+    def _eval_many(self, exprs, f: Frame) -> List[Val]:
+        """eval_expr of each; on the GPU the computed ones share launches."""
+        if self.device.type == "cuda":
+            return eval_exprs(exprs, f.cols, f.nrows, self.device,
+                              self.expr_stats)
+        return [eval_expr(e, f.cols, f.nrows, self.device) for e in exprs]
+
     def _exec_project(self, p: Project) -> Frame:
         f = self._exec(p.child)
         out = dict(f.cols) if p.extend else {}
-        for name, e in p.outs:
-            out[name] = eval_expr(_wrap(e), f.cols, f.nrows, self.device)
+        vals = self._eval_many([_wrap(e) for _, e in p.outs], f)
+        for (name, _), v in zip(p.outs, vals):
+            out[name] = v
         return Frame(out, f.nrows, f.sharded)
 
     def _exec_join(self, p: Join) -> Frame:
@@ -654,9 +670,10 @@ class Engine:
 
         native = []          # (fn, Val|None)
         slots = []           # per plain agg: dict of native indices
+        args = iter(self._eval_many(
+            [_wrap(e) for _, _, e in plain if e is not None], f))
         for name, fn, e in plain:
-            v = (eval_expr(_wrap(e), f.cols, f.nrows, self.device)
-                 if e is not None else None)
+            v = next(args) if e is not None else None
             if fn == "count":
                 if v is None:
                     slots.append({"fn": fn, "n": self._push(native, ("count",
