@@ -331,6 +331,58 @@ def expr_bench(n, dev, g):
                 "ms_max": round(xs[-1] * 1e3, 4)}), flush=True)
 
 
+def groupby_sorted_bench(n, dev, g):
+    """ops.aggregate.groupby (hash table) against groupby_sorted (sort plus
+    segmented reduce) on the whole call, sort and host syncs included: what
+    the NDS engine pays per aggregate. A nullable float64 sum and a count
+    over four key sets."""
+    from spark_rapids_jni_amd.columnar import Column, DType, Table
+    from spark_rapids_jni_amd.ops.aggregate import (Agg, _validity_from_bool,
+                                                    groupby, groupby_sorted)
+    ri = lambda hi: torch.randint(0, hi, (n,), device=dev, generator=g)
+    icol = lambda t, valid=None: Column(
+        DType.INT64, n, t, None if valid is None
+        else _validity_from_bool(valid), null_count=None)
+    # quarter-integers: every order of summation is exact
+    vdata = torch.randint(-400, 400, (n,), device=dev,
+                          generator=g).to(torch.float64) / 4
+    vvalid = torch.rand(n, device=dev, generator=g) < 0.9
+    vcol = Column(DType.FLOAT64, n, vdata, _validity_from_bool(vvalid),
+                  null_count=None)
+    aggs = [(Agg.SUM, vcol), (Agg.COUNT_ALL, None)]
+    fkey = torch.randint(0, 1000, (n,), device=dev,
+                         generator=g).to(torch.float64) / 8
+    knull = torch.rand(n, device=dev, generator=g) < 0.9
+    cases = {
+        "i64_100_groups": ([icol(ri(100))], None),
+        "i64_n4_groups": ([icol(ri(max(1, n // 4)))], None),
+        "dict3_one_nullable": ([icol(ri(8)), icol(ri(16), knull),
+                                icol(ri(4))], [10, 10, 10]),
+        "f64_generic": ([Column(DType.FLOAT64, n, fkey)], None),
+    }
+    reps = 20
+    inner = 20 if n <= 2**16 else 1
+    for name, (kcols, bits) in cases.items():
+        new = lambda: groupby_sorted(Table(kcols), aggs, key_bits=bits)
+        old = lambda: groupby(Table(kcols), aggs)
+        (nk, nr), (ok, orr) = new(), old()
+        assert nk.num_rows == ok.num_rows, name
+        for a, b in zip(nr, orr):
+            assert torch.equal(a.data.sum(), b.data.sum()), name
+        new_s, old_s = ab_time(new, old, inner, repeats=reps)
+        launches = {"sorted": count_launches(new),
+                    "hash": count_launches(old)}
+        for path, xs in (("sorted", new_s), ("hash", old_s)):
+            xs = sorted(xs)
+            print(json.dumps({
+                "bench": "groupby_sorted", "keys": name, "path": path,
+                "rows": n, "groups": nk.num_rows, "repeats": reps,
+                "launches": launches[path],
+                "ms": round(xs[len(xs) // 2] * 1e3, 4),
+                "ms_min": round(xs[0] * 1e3, 4),
+                "ms_max": round(xs[-1] * 1e3, 4)}), flush=True)
+
+
 def join_narrow_bench(nb, npr, iters, dev, g):
     """Narrow (8-byte slot) against wide (16-byte slot) join table on the same
     dense int64 keys, build and probe timed separately and alternating. The
@@ -401,10 +453,16 @@ def main():
     ap.add_argument("--rows", type=int, default=2**24)
     ap.add_argument("--iters", type=int, default=5)
     ap.add_argument("--only", choices=["sort_order", "join_narrow", "window",
-                                      "expr"],
+                                      "expr", "groupby_sorted"],
                     default=None,
                     help="run just this group")
     args = ap.parse_args()
+    if args.only == "groupby_sorted":
+        g = torch.Generator(device="cuda")
+        g.manual_seed(7)
+        for gn in (256, 2048, 2**16, 2**20, 2**24):
+            groupby_sorted_bench(gn, "cuda", g)
+        return
     if args.only == "window":
         g = torch.Generator(device="cuda")
         g.manual_seed(7)

@@ -248,8 +248,52 @@ def _precheck_all_true(vals):
             pass
 
 
+class GroupbyStats:
+    """Counts of the aggregation calls each GPU group-by path took."""
+
+    def __init__(self):
+        self.hash_calls = 0
+        self.sorted_calls = 0
+        self.global_calls = 0  # of sorted_calls: one segment, no sort
+
+
+# GPU group-by routing in "auto" mode, from the groupby_sorted table in
+# docs/PERF.md: frames of up to this many rows take the sort-based group-by
+# (ops/segmented.py), larger ones the hash table. At 256 and 2048 rows the
+# sorted path measured faster than the hash table by more than both spreads
+# on every key set; from 65536 rows up it lost on at least one key set (int64
+# and float64 keys at 65536, many groups at 2^20, a float64 key at 2^24).
+# 0 would mean: never in "auto" mode.
+SORTED_GROUPBY_MAX_ROWS = 2048
+GROUPBY_MODES = ("auto", "hash", "sorted")
+
+
 class GpuBackend:
-    """Joins and aggregations through the HIP kernels."""
+    """Joins and aggregations through the HIP kernels. `groupby_mode`:
+    "hash" is the hash table of ops/aggregate.py at every size, "sorted" the
+    sort-based group-by of ops/segmented.py at every size (deterministic
+    float sums, groups in key order), "auto" picks by SORTED_GROUPBY_MAX_ROWS.
+    `ordered_joins` gives every join's output a fixed row order."""
+
+    def __init__(self, groupby_mode: str = "auto", device="cuda",
+                 ordered_joins: bool = False):
+        if groupby_mode not in GROUPBY_MODES:
+            raise ValueError(f"groupby_mode must be one of {GROUPBY_MODES}, "
+                             f"got {groupby_mode!r}")
+        self.groupby_mode = groupby_mode
+        self.device = torch.device(device)
+        # the probe kernels place each wave's matches at an atomic cursor, so
+        # the ORDER of a join's output rows differs run to run; True sorts
+        # the pairs by (left row, right row): the sorted group-by downstream
+        # then sums every group in the same order on every run
+        self.ordered_joins = ordered_joins
+        self.groupby_stats = GroupbyStats()
+
+    def uses_sorted(self, nrows: int) -> bool:
+        """Whether a group-by over nrows rows takes the sorted path."""
+        if self.groupby_mode == "auto":
+            return 0 < nrows <= SORTED_GROUPBY_MAX_ROWS
+        return self.groupby_mode == "sorted"
 
     def join(self, left_keys: List[Val], right_keys: List[Val], how: str,
              nleft: int):
@@ -270,23 +314,80 @@ class GpuBackend:
                 return sel, None
             tbl = HashJoinTable.build(bcols)
             sel = tbl.semi_join(pcols, anti=(how == "anti"))
+            if self.ordered_joins:
+                sel = torch.sort(sel)[0]
             return sel, None
         tbl = HashJoinTable.build(bcols)
         if how == "full":
             from ..ops.join import make_full_outer, make_left_outer
             bi, pi, matched = tbl.inner_join(pcols, track_build_matches=True)
+            bi, pi = self._ordered_pairs(bi, pi, nleft)
             fb, fp = make_full_outer(matched, bi, pi, nleft)
             return fp, fb  # -1 entries on both sides
         bi, pi = tbl.inner_join(pcols)
+        bi, pi = self._ordered_pairs(bi, pi, nleft)
         if how == "left":
             from ..ops.join import make_left_outer
             lb, lp = make_left_outer(nleft, bi, pi)
             return lp, lb  # (left_idx, right_idx with -1 for unmatched)
         return pi, bi.long()
 
-    def groupby(self, keys: List[Val], aggs, hint=None):
+    def _ordered_pairs(self, bi, pi, nleft: int):
+        """The matches of an inner join sorted by (left row, right row)."""
+        if not self.ordered_joins or pi.numel() < 2:
+            return bi, pi
+        from ..ops.sort import sort_order_tensors
+        order = sort_order_tensors(
+            [pi, bi], key_bits=[max(1, (max(nleft, 1) - 1).bit_length()),
+                                None])
+        return bi[order], pi[order]
+
+    def _groupby_sorted(self, keys: List[Val], aggs, nrows: int):
+        from ..ops.segmented import groupby_tensors
+        self.groupby_stats.sorted_calls += 1
+        if not keys:
+            self.groupby_stats.global_calls += 1
+        funcs = []
+        for fn, v in aggs:
+            if v is None:
+                funcs.append(("count", None, None))
+            else:
+                funcs.append(("count" if fn == "count_valid" else fn,
+                              v.data, v.valid))
+        if keys or any(v is not None for _fn, v in aggs):
+            first, res, ng = groupby_tensors(
+                [v.data for v in keys], funcs, [v.valid for v in keys],
+                # dictionary codes only sort the bits their dictionary needs
+                [None if v.dict is None or v.data.dtype.is_floating_point
+                 or v.data.dtype == torch.bool
+                 else max(1, (len(v.dict) - 1).bit_length()) for v in keys])
+        else:  # count(*) alone over no key: nothing to read
+            ng = 1 if nrows else 0
+            dev = self.device
+            first = torch.zeros(ng, dtype=torch.int64, device=dev)
+            res = [(torch.full((ng,), nrows, dtype=torch.int64, device=dev),
+                    None) for _ in funcs]
+        out_keys = [Val(v.data[first],
+                        v.valid[first] if v.valid is not None else None,
+                        v.dict) for v in keys]
+        out_res = []
+        for data, valid in res:
+            # the dtypes of the hash path: int64 or float64
+            wide = torch.float64 if data.dtype.is_floating_point \
+                else torch.int64
+            out_res.append(Val(data.to(wide), valid))
+        return out_keys, out_res, ng
+
+    def groupby(self, keys: List[Val], aggs, hint=None, nrows=None):
         """aggs: list of (fn∈{count,count_valid,sum,min,max}, Val|None).
-        Returns (key Vals, result Vals)."""
+        Returns (key Vals, result Vals, ngroups). An empty key list is one
+        global group over `nrows` rows; only the sorted path takes it."""
+        if nrows is None:
+            nrows = keys[0].data.numel() if keys else next(
+                (v.data.numel() for _fn, v in aggs if v is not None), 0)
+        if not keys or self.uses_sorted(nrows):
+            return self._groupby_sorted(keys, aggs, nrows)
+        self.groupby_stats.hash_calls += 1
         from ..columnar import validity_to_bool
         from ..ops.aggregate import Agg as A, groupby as gb
         _precheck_all_true(list(keys) + [v for _fn, v in aggs])
@@ -497,14 +598,24 @@ _WINDOW_NULL_FILL = {"sum": 0.0, "cumsum": 0.0, "avg": 0.0,
 
 class Engine:
     def __init__(self, catalog, device="cuda", world: int = 1, rank: int = 0,
-                 backend=None):
-        """catalog: dict name -> Dataset (see schema.py) or Frame."""
+                 backend=None, deterministic: bool = False):
+        """catalog: dict name -> Dataset (see schema.py) or Frame.
+        deterministic: on CUDA every aggregate takes the sort-based group-by
+        and every join's output is put in a fixed row order
+        (GpuBackend("sorted", ordered_joins=True)), so float sums are the
+        same bits on every run; the CPU backend is deterministic as it
+        is."""
         self.catalog = catalog
         self.device = torch.device(device)
         self.world = world
         self.rank = rank
-        self.backend = backend or (GpuBackend() if self.device.type == "cuda"
-                                   else CpuBackend())
+        self.backend = backend or (
+            GpuBackend("sorted" if deterministic else "auto", self.device,
+                       ordered_joins=deterministic)
+            if self.device.type == "cuda" else CpuBackend())
+        # CUDA group-by route: calls per path (all zero on other backends)
+        self.groupby_stats = getattr(self.backend, "groupby_stats",
+                                     None) or GroupbyStats()
         self.temps: Dict[str, Frame] = {}
         self._scan_cache: Dict[str, Frame] = {}
         # CUDA expression route: kernel calls, and the fallbacks to the
@@ -699,10 +810,20 @@ class Engine:
                 raise ValueError(fn)
         if not native:
             native.append(("count", None))  # keys-only: need group discovery
-        # a global aggregate has exactly one group: the hint engages the
-        # LDS pre-aggregation kernel instead of a per-row contended CAS
-        # table; chunk to <=3 aggs per pass (the LDS kernel's limit)
-        if dummy_key:
+        # the sort-based group-by takes a global aggregate as an empty key
+        # list: one segment over the identity order, no sort, no chunking
+        uses_sorted = getattr(self.backend, "uses_sorted", None)
+        sorted_global = (dummy_key and uses_sorted is not None
+                         and uses_sorted(f.nrows))
+        if sorted_global:
+            _k, rvals, ng = self.backend.groupby([], native, nrows=f.nrows)
+            kvals = [Val(torch.zeros(ng, dtype=torch.int64,
+                                     device=self.device))]
+        # on the hash path a global aggregate has exactly one group: the
+        # hint engages the LDS pre-aggregation kernel instead of a per-row
+        # contended CAS table; chunk to <=3 aggs per pass (the LDS kernel's
+        # limit)
+        elif dummy_key:
             # chunk by EFFECTIVE agg count: a nullable SUM/MIN/MAX carries a
             # hidden count_valid stream inside the kernel, so it costs 2 of
             # the LDS kernel's <=3 agg slots (q97 postmortem: 3 sums over

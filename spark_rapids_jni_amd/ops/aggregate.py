@@ -308,3 +308,78 @@ def _validity_from_bool(flags: torch.Tensor):
                            device=dev)
     packed = (bits.view(-1, 8).to(torch.uint8) * weights).sum(1, dtype=torch.uint8)
     return packed
+
+
+def groupby_sorted(keys, aggs: Sequence[Tuple[Agg, Optional[Column]]],
+                   key_bits: Optional[Sequence] = None):
+    """Sort-based `groupby`: the same arguments, return shape and result
+    dtypes (COUNT int64; SUM int64 or float64; MIN and MAX widened to int64 or
+    float64; packed validity, null results for all-null groups), through
+    ops/segmented.py `groupby_tensors` instead of the hash table.
+
+    Unlike `groupby` the groups come out in ascending key order, nulls
+    first; float sums combine in input row order, so the same input gives
+    the same bits on every run; no atomics and one host sync. Key columns
+    are those `sort_order` supports (DECIMAL128 through its two-field
+    encoding), with the sort's equality: nulls equal each other, all NaNs
+    equal, -0.0 == 0.0. `key_bits[i] = b` is the promise of
+    `sort_order_tensors` for the i-th key column (dictionary codes within
+    0 .. 2**b - 1): only b bits are sorted.
+    """
+    from ..columnar import validity_to_bool
+    from .segmented import _VALUE_KINDS, segmented_reduce_tensors
+    from .sort import (_SK_SINT, _SK_UINT, _key_change_keys,
+                       _sort_order_keys, _table_keys)
+    kcols = keys.columns if isinstance(keys, Table) else (
+        [keys] if isinstance(keys, Column) else list(keys))
+    n = kcols[0].size
+    dev = torch.device(kcols[0].device)
+    funcs = []
+    for i, (op, col) in enumerate(aggs):
+        if op == Agg.COUNT_ALL:
+            funcs.append(("count", None, None))
+            continue
+        if col is None:
+            raise ValueError(f"aggs[{i}]: {Agg(op).name} needs a column")
+        if col.data is None or col.data.dtype not in _VALUE_KINDS or \
+                col.data.numel() != col.size:
+            raise NotImplementedError(
+                f"groupby_sorted: {col.dtype.name} values are not supported")
+        valid = (validity_to_bool(col.validity, col.size)
+                 if col.validity is not None else None)
+        fn = {Agg.COUNT_VALID: "count", Agg.SUM: "sum", Agg.MIN: "min",
+              Agg.MAX: "max"}[Agg(op)]
+        funcs.append((fn, col.data, valid))
+    if key_bits is not None and len(key_bits) != len(kcols):
+        raise ValueError(f"key_bits has {len(key_bits)} entries for "
+                         f"{len(kcols)} keys")
+    ks = []
+    for i, c in enumerate(kcols):
+        one = _table_keys(Table([c]), None, None)
+        b = key_bits[i] if key_bits is not None else None
+        if b is not None:
+            if not 1 <= int(b) <= 64:
+                raise ValueError(f"key_bits[{i}] = {b} is outside 1..64")
+            if len(one) == 1 and one[0].kind == _SK_SINT and \
+                    int(b) < one[0].bits:
+                one[0].kind, one[0].bits = _SK_UINT, int(b)
+        ks += one
+    if n == 0:
+        head = torch.zeros(0, dtype=torch.bool, device=dev)
+        first, res, _count = segmented_reduce_tensors(head, funcs, None, 0)
+        ngroups = 0
+    else:
+        perm = _sort_order_keys(ks, n, dev)
+        head = _key_change_keys(ks, perm, n)
+        ngroups = int(head.sum().item())  # the one sync
+        first, res, _count = segmented_reduce_tensors(head, funcs, perm,
+                                                      ngroups)
+    key_out = Table([gather_column(c, first) for c in kcols])
+    results: List[Column] = []
+    for data, valid in res:
+        wide = torch.float64 if data.dtype.is_floating_point else torch.int64
+        dt = DType.FLOAT64 if wide == torch.float64 else DType.INT64
+        mask = _validity_from_bool(valid) if valid is not None else None
+        results.append(Column(dt, ngroups, data.to(wide), mask,
+                              null_count=None))
+    return key_out, results
