@@ -327,7 +327,8 @@ def groupby_sorted(keys, aggs: Sequence[Tuple[Agg, Optional[Column]]],
     0 .. 2**b - 1): only b bits are sorted.
     """
     from ..columnar import validity_to_bool
-    from .segmented import _VALUE_KINDS, segmented_reduce_tensors
+    from ._segscan import _VALUE_KINDS
+    from .segmented import segmented_reduce_tensors
     from .sort import (_SK_SINT, _SK_UINT, _key_change_keys,
                        _sort_order_keys, _table_keys)
     kcols = keys.columns if isinstance(keys, Table) else (

@@ -28,21 +28,10 @@ from typing import List, Optional, Sequence, Tuple
 import torch
 
 from .. import _native
-
-# mirrors of src/gpu/seg_reduce.hpp
-SEG_MAX_FUNCS = 8
-SMALL_ROWS = 2048
-TILE_ROWS = 2048
-CARRY_CHUNK = 1024  # tile carries per round of the carry scan
-
-_FUNCS = {"count": 0, "sum": 1, "min": 2, "max": 3, "avg": 4}
-_SRK_NONE, _SRK_BOOL, _SRK_SINT, _SRK_F32, _SRK_F64 = range(5)
-_VALUE_KINDS = {
-    torch.bool: _SRK_BOOL, torch.int8: _SRK_SINT, torch.int16: _SRK_SINT,
-    torch.int32: _SRK_SINT, torch.int64: _SRK_SINT, torch.float32: _SRK_F32,
-    torch.float64: _SRK_F64,
-}
-_BYTE_DTYPES = (torch.bool, torch.uint8, torch.int8)
+from ._segscan import (CARRY_CHUNK, SMALL_ROWS, TILE_ROWS,  # noqa: F401
+                       _AGGREGATES, _BYTE_DTYPES, _Func,
+                       _check_values, _descriptor, _outputs, _work_buffer)
+from ._segscan import MAX_FUNCS as SEG_MAX_FUNCS
 
 
 def seg_reduce_work_bytes(m: int, nfuncs: int) -> int:
@@ -51,64 +40,15 @@ def seg_reduce_work_bytes(m: int, nfuncs: int) -> int:
     return _native.gpu().seg_reduce_work_bytes(m, nfuncs)
 
 
-class _Func:
-    __slots__ = ("fn", "values", "valid")
-
-    def __init__(self, fn, values, valid):
-        self.fn, self.values, self.valid = fn, values, valid
-
-    def out_dtype(self):
-        if self.fn == "count":
-            return torch.int64
-        if self.fn == "avg":
-            return torch.float64
-        if self.fn == "sum":
-            return (torch.float64 if self.values.dtype.is_floating_point
-                    else torch.int64)
-        return self.values.dtype
-
-    def nullable(self):
-        return self.fn != "count" and self.valid is not None
-
-
 def _check_funcs(funcs, m, dev) -> List[_Func]:
     out = []
     for i, spec in enumerate(funcs):
         if len(spec) != 3:
             raise ValueError(f"funcs[{i}] must be (fn, values, valid)")
         fn, values, valid = spec
-        if fn not in _FUNCS:
+        if fn not in _AGGREGATES:  # the ranking functions are the window's
             raise ValueError(f"funcs[{i}]: unknown function {fn!r}")
-        if values is None:
-            if fn != "count":
-                raise ValueError(f"funcs[{i}]: {fn} needs values")
-        else:
-            if not isinstance(values, torch.Tensor):
-                raise TypeError(f"funcs[{i}]: values must be a torch.Tensor")
-            if values.dtype not in _VALUE_KINDS:
-                raise TypeError(f"funcs[{i}]: unsupported dtype "
-                                f"{values.dtype}")
-            if values.dim() != 1:
-                raise ValueError(f"funcs[{i}]: values must be 1-D, got shape "
-                                 f"{tuple(values.shape)}")
-            if values.numel() != m:
-                raise ValueError(f"funcs[{i}]: values has {values.numel()} "
-                                 f"rows but head_flags has {m}")
-            if values.device != dev:
-                raise ValueError(f"funcs[{i}]: values and head_flags are on "
-                                 "different devices")
-        if valid is not None:
-            if not isinstance(valid, torch.Tensor) or \
-                    valid.dtype not in _BYTE_DTYPES:
-                raise TypeError(f"funcs[{i}]: valid must be a bool, uint8 or "
-                                "int8 tensor")
-            if valid.dim() != 1 or valid.numel() != m:
-                raise ValueError(f"funcs[{i}]: valid must be 1-D with {m} "
-                                 "rows")
-            if valid.device != dev:
-                raise ValueError(f"funcs[{i}]: valid and head_flags are on "
-                                 "different devices")
-            valid = valid.contiguous()
+        valid = _check_values(i, fn, values, valid, m, dev, "head_flags")
         out.append(_Func(fn, values, valid))
     return out
 
@@ -191,35 +131,13 @@ def _reduce_gpu(head, perm, fs: List[_Func], k):
     stream = _native.current_stream()
     first = torch.empty(k, dtype=torch.int64, device=dev)
     count = torch.empty(1, dtype=torch.int64, device=dev)
-    results = []
-    for f in fs:
-        data = torch.empty(k, dtype=f.out_dtype(), device=dev)
-        ov = (torch.empty(k, dtype=torch.bool, device=dev)
-              if f.nullable() else None)
-        results.append((data, ov))
+    results = [_outputs(f, k, dev) for f in fs]
     # without output rows only the count is wanted
     todo = list(zip(fs, results)) if k > 0 else []
     for lo in range(0, max(len(todo), 1), SEG_MAX_FUNCS):
         chunk = todo[lo:lo + SEG_MAX_FUNCS]
-        descs = []
-        for f, (data, ov) in chunk:
-            if f.values is None:
-                kind, width, stride, vptr = _SRK_NONE, 1, 1, 0
-            else:
-                kind = _VALUE_KINDS[f.values.dtype]
-                width = f.values.element_size()
-                stride = f.values.stride(0) if m > 1 else 1
-                if stride < 1:
-                    f.values = f.values.contiguous()
-                    stride = 1
-                vptr = f.values.data_ptr()
-            descs.append((_FUNCS[f.fn], kind, width, stride, vptr,
-                          f.valid.data_ptr() if f.valid is not None else 0,
-                          data.data_ptr(),
-                          ov.data_ptr() if ov is not None else 0))
-        nbytes = g.seg_reduce_work_bytes(m, len(chunk))
-        work = torch.empty(nbytes // 8, dtype=torch.int64, device=dev) \
-            if nbytes else None
+        descs = [_descriptor(f, m, data, ov) for f, (data, ov) in chunk]
+        work = _work_buffer(g.seg_reduce_work_bytes(m, len(chunk)), dev)
         g.seg_reduce(descs, perm.data_ptr() if perm is not None else 0,
                      head.data_ptr(), m, m, k, first.data_ptr() if k else 0,
                      count.data_ptr(),
@@ -276,9 +194,7 @@ def segmented_reduce_tensors(head_flags: torch.Tensor, funcs: Sequence[Tuple],
     k = m if num_segments is None else num_segments
     if m == 0:
         return (torch.empty(0, dtype=torch.int64, device=dev),
-                [(torch.empty(0, dtype=f.out_dtype(), device=dev),
-                  torch.empty(0, dtype=torch.bool, device=dev)
-                  if f.nullable() else None) for f in fs],
+                [_outputs(f, 0, dev) for f in fs],
                 torch.zeros(1, dtype=torch.int64, device=dev))
     head = head_flags.contiguous()
     if dev.type == "cuda":

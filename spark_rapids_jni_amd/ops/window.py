@@ -30,51 +30,16 @@ import torch
 
 from .. import _native
 from ..columnar import Column, DType, Table, validity_to_bool
-
-# mirrors of src/gpu/window.hpp
-WINDOW_MAX_FUNCS = 8
-SMALL_ROWS = 2048
-TILE_ROWS = 2048
-CARRY_CHUNK = 1024  # tile carries per round of the carry scan
-
-_FUNCS = {"row_number": 0, "rank": 1, "dense_rank": 2, "count": 3, "sum": 4,
-          "min": 5, "max": 6, "avg": 7}
-_RANKING = ("row_number", "rank", "dense_rank")
-_FRAMES = {"partition": 0, "rows": 1, "range": 2}
-_WK_NONE, _WK_BOOL, _WK_SINT, _WK_F32, _WK_F64 = range(5)
-_VALUE_KINDS = {
-    torch.bool: _WK_BOOL, torch.int8: _WK_SINT, torch.int16: _WK_SINT,
-    torch.int32: _WK_SINT, torch.int64: _WK_SINT, torch.float32: _WK_F32,
-    torch.float64: _WK_F64,
-}
-_BYTE_DTYPES = (torch.bool, torch.uint8, torch.int8)
+from ._segscan import (CARRY_CHUNK, SMALL_ROWS, TILE_ROWS,  # noqa: F401
+                       _BYTE_DTYPES, _FRAMES, _FUNCS, _RANKING, _Func,
+                       _check_values, _descriptor, _outputs, _work_buffer)
+from ._segscan import MAX_FUNCS as WINDOW_MAX_FUNCS
 
 
 def window_work_bytes(m: int, nfuncs: int) -> int:
     """Bytes of scratch one kernel call over m rows and nfuncs functions
     takes (zero on the one-workgroup path)."""
     return _native.gpu().window_work_bytes(m, nfuncs)
-
-
-class _Func:
-    __slots__ = ("fn", "values", "valid", "frame")
-
-    def __init__(self, fn, values, valid, frame):
-        self.fn, self.values, self.valid, self.frame = fn, values, valid, frame
-
-    def out_dtype(self):
-        if self.fn in _RANKING or self.fn == "count":
-            return torch.int64
-        if self.fn == "avg":
-            return torch.float64
-        if self.fn == "sum":
-            return (torch.float64 if self.values.dtype.is_floating_point
-                    else torch.int64)
-        return self.values.dtype
-
-    def nullable(self):
-        return (self.fn not in _RANKING and self.fn != "count"
-                and self.valid is not None)
 
 
 def _check_flags(t, what, m, dev):
@@ -104,36 +69,7 @@ def _check_funcs(funcs, m, dev, have_peer) -> List[_Func]:
             continue
         if frame not in _FRAMES:
             raise ValueError(f"funcs[{i}]: unknown frame {frame!r}")
-        if values is None:
-            if fn != "count":
-                raise ValueError(f"funcs[{i}]: {fn} needs values")
-        else:
-            if not isinstance(values, torch.Tensor):
-                raise TypeError(f"funcs[{i}]: values must be a torch.Tensor")
-            if values.dtype not in _VALUE_KINDS:
-                raise TypeError(f"funcs[{i}]: unsupported dtype "
-                                f"{values.dtype}")
-            if values.dim() != 1:
-                raise ValueError(f"funcs[{i}]: values must be 1-D, got shape "
-                                 f"{tuple(values.shape)}")
-            if values.numel() != m:
-                raise ValueError(f"funcs[{i}]: values has {values.numel()} "
-                                 f"rows but perm has {m}")
-            if values.device != dev:
-                raise ValueError(f"funcs[{i}]: values and perm are on "
-                                 "different devices")
-        if valid is not None:
-            if not isinstance(valid, torch.Tensor) or \
-                    valid.dtype not in _BYTE_DTYPES:
-                raise TypeError(f"funcs[{i}]: valid must be a bool, uint8 or "
-                                "int8 tensor")
-            if valid.dim() != 1 or valid.numel() != m:
-                raise ValueError(f"funcs[{i}]: valid must be 1-D with {m} "
-                                 "rows")
-            if valid.device != dev:
-                raise ValueError(f"funcs[{i}]: valid and perm are on "
-                                 "different devices")
-            valid = valid.contiguous()
+        valid = _check_values(i, fn, values, valid, m, dev, "perm")
         out.append(_Func(fn, values, valid, frame))
     return out
 
@@ -257,28 +193,10 @@ def _window_gpu(perm, part, peer, fs: List[_Func], have_peer):
         chunk = fs[lo:lo + WINDOW_MAX_FUNCS]
         descs = []
         for f in chunk:
-            data = torch.empty(m, dtype=f.out_dtype(), device=dev)
-            ov = (torch.empty(m, dtype=torch.bool, device=dev)
-                  if f.nullable() else None)
-            if f.values is None:
-                kind, width, stride, vptr = _WK_NONE, 1, 1, 0
-            else:
-                kind = _VALUE_KINDS[f.values.dtype]
-                width = f.values.element_size()
-                stride = f.values.stride(0) if m > 1 else 1
-                if stride < 1:
-                    f.values = f.values.contiguous()
-                    stride = 1
-                vptr = f.values.data_ptr()
-            descs.append((_FUNCS[f.fn], _FRAMES[f.frame], kind, width, stride,
-                          vptr,
-                          f.valid.data_ptr() if f.valid is not None else 0,
-                          data.data_ptr(),
-                          ov.data_ptr() if ov is not None else 0))
+            data, ov = _outputs(f, m, dev)
+            descs.append(_descriptor(f, m, data, ov))
             results.append((data, ov))
-        nbytes = g.window_work_bytes(m, len(chunk))
-        work = torch.empty(nbytes // 8, dtype=torch.int64, device=dev) \
-            if nbytes else None
+        work = _work_buffer(g.window_work_bytes(m, len(chunk)), dev)
         g.window(descs, perm.data_ptr(), part.data_ptr(),
                  peer.data_ptr() if have_peer else 0, m,
                  work.data_ptr() if work is not None else 0, stream)
@@ -313,9 +231,7 @@ def window_tensors(perm: torch.Tensor, part_flags: torch.Tensor,
         else None
     fs = _check_funcs(list(funcs), m, dev, have_peer)
     if m == 0:
-        return [(torch.empty(0, dtype=f.out_dtype(), device=dev),
-                 torch.empty(0, dtype=torch.bool, device=dev)
-                 if f.nullable() else None) for f in fs]
+        return [_outputs(f, 0, dev) for f in fs]
     if not fs:
         return []
     perm = perm.contiguous()

@@ -12,8 +12,10 @@
 // segment, counted from 0 in sorted order.
 //
 // How it works:
-//  * ONE SCAN PER FUNCTION, the scan of window.hip: a forward segmented
-//    inclusive scan of a (valid count, accumulator) state. The thread that
+//  * ONE SCAN PER FUNCTION, the scan of seg_scan.hpp that window.hip runs
+//    too (state, operator, block scan, value load, aggregate store and carry
+//    scan are shared, not copied): a forward segmented inclusive scan of a
+//    (valid count, accumulator) state. The thread that
 //    holds the LAST position of a segment has the segment's final state and
 //    writes it to out[g]; g is the inclusive count of heads up to the
 //    position, minus one, from a plain prefix sum of the head flags. The
@@ -24,7 +26,7 @@
 //    per function, the state of the segment still open at its end, and once
 //    its head count (nonzero = "tile holds a head", the segmented operator's
 //    flag); (2) one workgroup scans the tile carries in chunks with a running
-//    carry (the structure of window_carry_kernel / block_scan_chunked) and
+//    carry (seg_carry_scan, the structure of block_scan_chunked) and
 //    turns the head counts into their exclusive sum, the base segment number
 //    of every tile; (3) every tile rescans with its carry-in and writes at
 //    the segment ends inside it. A segment that runs past a tile is written
@@ -38,220 +40,20 @@
 // positions, so perm is read 64 contiguous bytes per lane and the in-register
 // part of the scan needs no LDS. Unlike the window kernels no state is looked
 // up at another position, so LDS holds the four wave totals only.
-#include "srj_common.hpp"
-#include "seg_reduce.hpp"
+#include "seg_scan.hpp"
 
 namespace srj {
 
-constexpr int SEG_WAVES = DEFAULT_BLOCK / WAVE;  // 4
-
-static_assert(SEG_TILE_ROWS == DEFAULT_BLOCK * SEG_EPT, "tile");
 static_assert(SEG_EPT <= 32, "head flags of a thread are bits of a word");
-
-enum SegOp : int32_t {
-  SOP_COUNT,  // only the count
-  SOP_SUM_I,
-  SOP_SUM_F,
-  SOP_MIN_I,
-  SOP_MAX_I,
-  SOP_MIN_F,
-  SOP_MAX_F,
-};
-
-struct SegFuncs {
-  SegFunc f[SEG_MAX_FUNCS];
-  int32_t nf;
-};
-
-// Scan state: head flag, valid values so far, accumulator (int64 or the bits
-// of a double, by the op).
-struct SegState {
-  int32_t flag;
-  int64_t cnt;
-  uint64_t acc;
-};
-
-__device__ inline bool seg_is_float(int32_t kind) {
-  return kind == SRK_F32 || kind == SRK_F64;
-}
-
-__device__ inline int32_t seg_op(const SegFunc& f) {
-  switch (f.fn) {
-    case SR_SUM: return seg_is_float(f.kind) ? SOP_SUM_F : SOP_SUM_I;
-    case SR_AVG: return SOP_SUM_F;
-    case SR_MIN: return seg_is_float(f.kind) ? SOP_MIN_F : SOP_MIN_I;
-    case SR_MAX: return seg_is_float(f.kind) ? SOP_MAX_F : SOP_MAX_I;
-    default: return SOP_COUNT;
-  }
-}
-
-__device__ inline double seg_f64(uint64_t b) {
-  return __longlong_as_double((long long)b);
-}
-__device__ inline uint64_t seg_bits(double d) {
-  return (uint64_t)__double_as_longlong(d);
-}
-
-// Spark order: NaN is greater than every value.
-__device__ inline double seg_max_f(double a, double b) {
-  if (a != a) return a;
-  if (b != b) return b;
-  return a > b ? a : b;
-}
-__device__ inline double seg_min_f(double a, double b) {
-  if (a != a) return b;
-  if (b != b) return a;
-  return a < b ? a : b;
-}
-
-// Segmented combine, a to the left of b: b wins outright if it carries a
-// head flag. The identity is (no flag, count 0, acc 0): +0.0 for the sums,
-// and min / max ignore the accumulator of a side with count 0.
-__device__ inline SegState seg_combine(int32_t op, const SegState& a,
-                                       const SegState& b) {
-  if (b.flag) return b;
-  SegState r;
-  r.flag = a.flag;
-  r.cnt = a.cnt + b.cnt;
-  switch (op) {
-    case SOP_COUNT:
-      r.acc = 0;
-      break;
-    case SOP_SUM_I:
-      r.acc = a.acc + b.acc;  // wraps
-      break;
-    case SOP_SUM_F:
-      r.acc = seg_bits(seg_f64(a.acc) + seg_f64(b.acc));
-      break;
-    default:
-      if (a.cnt == 0) {
-        r.acc = b.acc;
-      } else if (b.cnt == 0) {
-        r.acc = a.acc;
-      } else if (op == SOP_MIN_I) {
-        r.acc = (int64_t)a.acc < (int64_t)b.acc ? a.acc : b.acc;
-      } else if (op == SOP_MAX_I) {
-        r.acc = (int64_t)a.acc > (int64_t)b.acc ? a.acc : b.acc;
-      } else if (op == SOP_MIN_F) {
-        r.acc = seg_bits(seg_min_f(seg_f64(a.acc), seg_f64(b.acc)));
-      } else {
-        r.acc = seg_bits(seg_max_f(seg_f64(a.acc), seg_f64(b.acc)));
-      }
-      break;
-  }
-  return r;
-}
-
-__device__ inline SegState seg_shfl_up(const SegState& s, int off) {
-  SegState r;
-  r.flag = __shfl_up(s.flag, off, WAVE);
-  r.cnt = (int64_t)__shfl_up((long long)s.cnt, off, WAVE);
-  r.acc = (uint64_t)__shfl_up((long long)s.acc, off, WAVE);
-  return r;
-}
-
-// Exclusive segmented prefix of `agg` over the DEFAULT_BLOCK threads in
-// thread order, with `carry` combined in front of thread 0; *total is carry
-// combined with every thread (the same in all threads). One barrier, between
-// the write of wt and its reads; the caller owes one before the next call.
-__device__ inline SegState seg_block_scan(int32_t op, const SegState& agg,
-                                          const SegState& carry,
-                                          SegState (&wt)[SEG_WAVES],
-                                          SegState* total) {
-  const int lane = threadIdx.x & (WAVE - 1);
-  const int wave = threadIdx.x / WAVE;
-  SegState inc = agg;
-#pragma unroll
-  for (int off = 1; off < WAVE; off <<= 1) {
-    const SegState o = seg_shfl_up(inc, off);
-    if (lane >= off) inc = seg_combine(op, o, inc);
-  }
-  if (lane == WAVE - 1) wt[wave] = inc;
-  __syncthreads();
-  SegState pre = carry, tot = carry;
-#pragma unroll
-  for (int w = 0; w < SEG_WAVES; ++w) {
-    const SegState t = wt[w];
-    if (w < wave) pre = seg_combine(op, pre, t);
-    tot = seg_combine(op, tot, t);
-  }
-  const SegState ex = seg_shfl_up(inc, 1);
-  if (lane > 0) pre = seg_combine(op, pre, ex);
-  *total = tot;
-  return pre;
-}
-
-__device__ inline int64_t seg_load_int(const void* p, int64_t e, int32_t kind,
-                                       int32_t width) {
-  if (kind == SRK_BOOL) return static_cast<const uint8_t*>(p)[e] != 0;
-  switch (width) {
-    case 1: return static_cast<const int8_t*>(p)[e];
-    case 2: return static_cast<const int16_t*>(p)[e];
-    case 4: return static_cast<const int32_t*>(p)[e];
-    default: return static_cast<const int64_t*>(p)[e];
-  }
-}
-
-// The scan input of function f at a sorted position that holds row `row`
-// (-1: no row of the column there).
-__device__ inline SegState seg_item(const SegFunc& f, int32_t op, int64_t row,
-                                    bool head) {
-  SegState x;
-  x.flag = head;
-  x.cnt = 0;
-  x.acc = 0;
-  if (row < 0) return x;
-  if (f.valid != nullptr && f.valid[row] == 0) return x;
-  x.cnt = 1;
-  if (op == SOP_COUNT) return x;
-  const int64_t e = row * f.stride;
-  if (op == SOP_SUM_I || op == SOP_MIN_I || op == SOP_MAX_I) {
-    x.acc = (uint64_t)seg_load_int(f.values, e, f.kind, f.width);
-  } else {
-    double d;
-    if (f.kind == SRK_F32) {
-      d = static_cast<const float*>(f.values)[e];
-    } else if (f.kind == SRK_F64) {
-      d = static_cast<const double*>(f.values)[e];
-    } else {
-      d = (double)seg_load_int(f.values, e, f.kind, f.width);
-    }
-    x.acc = seg_bits(d);
-  }
-  return x;
-}
 
 // out[g] of function f from the state at the segment's last position.
 __device__ inline void seg_store(const SegFunc& f, int64_t g, int64_t cnt,
                                  uint64_t acc) {
-  const bool has = cnt > 0;
-  switch (f.fn) {
-    case SR_COUNT:
-      static_cast<int64_t*>(f.out)[g] = cnt;
-      return;
-    case SR_SUM:
-      static_cast<uint64_t*>(f.out)[g] = has ? acc : 0ull;
-      break;
-    case SR_AVG:
-      static_cast<double*>(f.out)[g] = has ? seg_f64(acc) / (double)cnt : 0.0;
-      break;
-    default:  // min, max: the dtype of the input
-      if (f.kind == SRK_F32) {
-        static_cast<float*>(f.out)[g] = has ? (float)seg_f64(acc) : 0.0f;
-      } else if (f.kind == SRK_F64) {
-        static_cast<uint64_t*>(f.out)[g] = has ? acc : 0ull;
-      } else {
-        const uint64_t v = has ? acc : 0ull;
-        switch (f.width) {
-          case 1: static_cast<uint8_t*>(f.out)[g] = (uint8_t)v; break;
-          case 2: static_cast<uint16_t*>(f.out)[g] = (uint16_t)v; break;
-          case 4: static_cast<uint32_t*>(f.out)[g] = (uint32_t)v; break;
-          default: static_cast<uint64_t*>(f.out)[g] = v; break;
-        }
-      }
-      break;
+  if (f.fn == SF_COUNT) {
+    static_cast<int64_t*>(f.out)[g] = cnt;
+  } else {
+    seg_store_agg(f, g, cnt, acc);
   }
-  if (f.out_valid != nullptr) f.out_valid[g] = has ? 1 : 0;
 }
 
 // Work layout (int64 words, nt tiles, function f):
@@ -337,7 +139,7 @@ __global__ __launch_bounds__(DEFAULT_BLOCK) void seg_tile_kernel(
       SegState carry;
       carry.flag = 0;
       carry.cnt = 0;
-      carry.acc = 0;
+      carry.acc = seg_identity(op);
       if (EMIT && fw != nullptr) {
         carry.cnt = fw[2 * T];
         carry.acc = (uint64_t)fw[2 * T + 1];
@@ -345,7 +147,7 @@ __global__ __launch_bounds__(DEFAULT_BLOCK) void seg_tile_kernel(
       SegState s[SEG_EPT];
 #pragma unroll
       for (int k = 0; k < SEG_EPT; ++k) {
-        const SegState x = seg_item(f, op, row[k], (hf >> k) & 1u);
+        const SegState x = seg_value_item(f, op, row[k], (hf >> k) & 1u);
         s[k] = k == 0 ? x : seg_combine(op, s[k - 1], x);
       }
       SegState total;
@@ -376,51 +178,12 @@ __global__ __launch_bounds__(DEFAULT_BLOCK) void seg_carry_kernel(
     SegFuncs fs, int64_t nt, int64_t* work) {
   __shared__ SegState wt[SEG_WAVES];
   __shared__ int64_t wh[SEG_WAVES];
-  const int tid = threadIdx.x;
-  const int64_t nchunks = (nt + SEG_CARRY_CHUNK - 1) / SEG_CARRY_CHUNK;
   const int64_t* heads = work;
 
   for (int32_t fi = 0; fi < fs.nf; ++fi) {
-    const int32_t op = seg_op(fs.f[fi]);
     int64_t* fw = work + nt + fi * seg_func_words(nt);
-    SegState carry;
-    carry.flag = 0;
-    carry.cnt = 0;
-    carry.acc = 0;
-    for (int64_t c = 0; c < nchunks; ++c) {
-      const int64_t t0 =
-          c * SEG_CARRY_CHUNK + (int64_t)tid * SEG_CARRY_PER_THREAD;
-      SegState s[SEG_CARRY_PER_THREAD];
-#pragma unroll
-      for (int k = 0; k < SEG_CARRY_PER_THREAD; ++k) {
-        const int64_t T = t0 + k;
-        SegState x;
-        x.flag = 0;
-        x.cnt = 0;
-        x.acc = 0;
-        if (T < nt) {
-          x.flag = heads[T] != 0;
-          x.cnt = fw[2 * T];
-          x.acc = (uint64_t)fw[2 * T + 1];
-        }
-        s[k] = k == 0 ? x : seg_combine(op, s[k - 1], x);
-      }
-      SegState total;
-      const SegState pre =
-          seg_block_scan(op, s[SEG_CARRY_PER_THREAD - 1], carry, wt, &total);
-#pragma unroll
-      for (int k = 0; k < SEG_CARRY_PER_THREAD; ++k) {
-        const int64_t T = t0 + k;
-        if (T >= nt) continue;
-        // the state at the last row of tile T - 1
-        const SegState ex = k == 0 ? pre : seg_combine(op, pre, s[k - 1]);
-        fw[2 * T] = ex.cnt;
-        fw[2 * T + 1] = (int64_t)ex.acc;
-      }
-      carry = total;
-      carry.flag = 0;
-      __syncthreads();  // wt is rewritten by the next chunk
-    }
+    seg_carry_scan(seg_op(fs.f[fi]), heads, fw, nt, wt,
+                   [](int64_t, const SegState&) {});
   }
   // last, the head counts become the base segment number of every tile (the
   // scans above read them as flags)

@@ -19,8 +19,11 @@
 //    partition (partition). row_number is the count of rows, dense_rank the
 //    count of peer heads, rank the row count minus the distance to the last
 //    peer head (a running maximum of head positions). The last positions
-//    come from a reverse scan of the next head position.
-//  * SMALL PATH (m <= WINDOW_SMALL_ROWS). One workgroup, one launch: the
+//    come from a reverse scan of the next head position. The state, the
+//    operator, the block scan, the value load and the aggregate store are
+//    those of seg_scan.hpp, shared with seg_reduce.hip; here are the ranking
+//    cases, the frame lookup and the reverse scan.
+//  * SMALL PATH (m <= SEG_SMALL_ROWS). One workgroup, one launch: the
 //    states of the tile sit in LDS and the frame ends index them.
 //  * TILED PATH. Three launches: (1) every tile scans itself and writes, per
 //    function, its carry, the state before its first partition head and the
@@ -38,169 +41,25 @@
 //    the position, so float sums are bit-identical run to run.
 //
 // MI355X notes: wave64 scans by __shfl_up/__shfl_down; a thread owns
-// WINDOW_EPT consecutive positions, so perm is read 64 contiguous bytes per
+// SEG_EPT consecutive positions, so perm is read 64 contiguous bytes per
 // lane and the in-register part of the scan needs no LDS. The LDS state
 // arrays are padded by one slot per 8 so the 64-byte lane stride does not
 // fold the lanes of a half-wave onto 8 banks.
-#include "srj_common.hpp"
-#include "window.hpp"
+#include "seg_scan.hpp"
 
 namespace srj {
 
-constexpr int WIN_WAVES = DEFAULT_BLOCK / WAVE;  // 4
-constexpr int32_t WIN_NONE = WINDOW_TILE_ROWS;   // no head later in the tile
-constexpr int WIN_SLOTS = WINDOW_TILE_ROWS + WINDOW_TILE_ROWS / 8;
+constexpr int32_t WIN_NONE = SEG_TILE_ROWS;  // no head later in the tile
+constexpr int WIN_SLOTS = SEG_TILE_ROWS + SEG_TILE_ROWS / 8;
 
-static_assert(WINDOW_EPT == 8, "lds_slot pads one slot per thread");
-static_assert(WINDOW_TILE_ROWS == DEFAULT_BLOCK * WINDOW_EPT, "tile");
-static_assert(WINDOW_TILE_ROWS < 65536, "next-head positions are 16-bit");
-
-enum WinOp : int32_t {
-  OP_COUNT,  // only the count
-  OP_RANK,   // count of rows; acc = position of the last peer head
-  OP_SUM_I,
-  OP_SUM_F,
-  OP_MIN_I,
-  OP_MAX_I,
-  OP_MIN_F,
-  OP_MAX_F,
-};
-
-struct WinFuncs {
-  WinFunc f[WINDOW_MAX_FUNCS];
-  int32_t nf;
-};
-
-// Scan state: head flag, valid values so far, accumulator (int64 or the bits
-// of a double, by the op).
-struct WinState {
-  int32_t flag;
-  int64_t cnt;
-  uint64_t acc;
-};
-
-__device__ inline bool win_is_float(int32_t kind) {
-  return kind == WK_F32 || kind == WK_F64;
-}
-
-__device__ inline int32_t win_op(const WinFunc& f) {
-  switch (f.fn) {
-    case WF_RANK: return OP_RANK;
-    case WF_SUM: return win_is_float(f.kind) ? OP_SUM_F : OP_SUM_I;
-    case WF_AVG: return OP_SUM_F;
-    case WF_MIN: return win_is_float(f.kind) ? OP_MIN_F : OP_MIN_I;
-    case WF_MAX: return win_is_float(f.kind) ? OP_MAX_F : OP_MAX_I;
-    default: return OP_COUNT;
-  }
-}
-
-__device__ inline uint64_t win_identity(int32_t op) {
-  return op == OP_RANK ? ~0ull : 0ull;  // position -1; +0.0; 0
-}
-
-__device__ inline double win_f64(uint64_t b) {
-  return __longlong_as_double((long long)b);
-}
-__device__ inline uint64_t win_bits(double d) {
-  return (uint64_t)__double_as_longlong(d);
-}
-
-// Spark order: NaN is greater than every value.
-__device__ inline double win_max_f(double a, double b) {
-  if (a != a) return a;
-  if (b != b) return b;
-  return a > b ? a : b;
-}
-__device__ inline double win_min_f(double a, double b) {
-  if (a != a) return b;
-  if (b != b) return a;
-  return a < b ? a : b;
-}
-
-// Segmented combine, a to the left of b: b wins outright if it carries a
-// head flag.
-__device__ inline WinState win_combine(int32_t op, const WinState& a,
-                                       const WinState& b) {
-  if (b.flag) return b;
-  WinState r;
-  r.flag = a.flag;
-  r.cnt = a.cnt + b.cnt;
-  switch (op) {
-    case OP_COUNT:
-      r.acc = 0;
-      break;
-    case OP_RANK:
-      r.acc = (int64_t)a.acc > (int64_t)b.acc ? a.acc : b.acc;
-      break;
-    case OP_SUM_I:
-      r.acc = a.acc + b.acc;  // wraps
-      break;
-    case OP_SUM_F:
-      r.acc = win_bits(win_f64(a.acc) + win_f64(b.acc));
-      break;
-    default:
-      if (a.cnt == 0) {
-        r.acc = b.acc;
-      } else if (b.cnt == 0) {
-        r.acc = a.acc;
-      } else if (op == OP_MIN_I) {
-        r.acc = (int64_t)a.acc < (int64_t)b.acc ? a.acc : b.acc;
-      } else if (op == OP_MAX_I) {
-        r.acc = (int64_t)a.acc > (int64_t)b.acc ? a.acc : b.acc;
-      } else if (op == OP_MIN_F) {
-        r.acc = win_bits(win_min_f(win_f64(a.acc), win_f64(b.acc)));
-      } else {
-        r.acc = win_bits(win_max_f(win_f64(a.acc), win_f64(b.acc)));
-      }
-      break;
-  }
-  return r;
-}
-
-__device__ inline WinState win_shfl_up(const WinState& s, int off) {
-  WinState r;
-  r.flag = __shfl_up(s.flag, off, WAVE);
-  r.cnt = (int64_t)__shfl_up((long long)s.cnt, off, WAVE);
-  r.acc = (uint64_t)__shfl_up((long long)s.acc, off, WAVE);
-  return r;
-}
-
-// Exclusive segmented prefix of `agg` over the DEFAULT_BLOCK threads in
-// thread order, with `carry` combined in front of thread 0; *total is carry
-// combined with every thread (the same in all threads). One barrier, between
-// the write of wt and its reads; the caller owes one before the next call.
-__device__ inline WinState win_block_scan(int32_t op, const WinState& agg,
-                                          const WinState& carry,
-                                          WinState (&wt)[WIN_WAVES],
-                                          WinState* total) {
-  const int lane = threadIdx.x & (WAVE - 1);
-  const int wave = threadIdx.x / WAVE;
-  WinState inc = agg;
-#pragma unroll
-  for (int off = 1; off < WAVE; off <<= 1) {
-    const WinState o = win_shfl_up(inc, off);
-    if (lane >= off) inc = win_combine(op, o, inc);
-  }
-  if (lane == WAVE - 1) wt[wave] = inc;
-  __syncthreads();
-  WinState pre = carry, tot = carry;
-#pragma unroll
-  for (int w = 0; w < WIN_WAVES; ++w) {
-    const WinState t = wt[w];
-    if (w < wave) pre = win_combine(op, pre, t);
-    tot = win_combine(op, tot, t);
-  }
-  const WinState ex = win_shfl_up(inc, 1);
-  if (lane > 0) pre = win_combine(op, pre, ex);
-  *total = tot;
-  return pre;
-}
+static_assert(SEG_EPT == 8, "lds_slot pads one slot per thread");
+static_assert(SEG_TILE_ROWS < 65536, "next-head positions are 16-bit");
 
 // Reverse exclusive minimum over the threads AFTER this one, of two values
 // at once (`none` where there is no later thread); *allp / *allq are the
-// minima over all threads. One barrier, as win_block_scan.
+// minima over all threads. One barrier, as seg_block_scan.
 __device__ inline void win_block_rmin2(int32_t& p, int32_t& q, int32_t none,
-                                       int32_t (&wm)[2][WIN_WAVES],
+                                       int32_t (&wm)[2][SEG_WAVES],
                                        int32_t* allp, int32_t* allq) {
   const int lane = threadIdx.x & (WAVE - 1);
   const int wave = threadIdx.x / WAVE;
@@ -224,7 +83,7 @@ __device__ inline void win_block_rmin2(int32_t& p, int32_t& q, int32_t none,
   if (lane == WAVE - 1) ep = eq = none;
   int32_t ap = none, aq = none;
 #pragma unroll
-  for (int w = 0; w < WIN_WAVES; ++w) {
+  for (int w = 0; w < SEG_WAVES; ++w) {
     const int32_t a = wm[0][w], b = wm[1][w];
     if (w > wave) {
       ep = a < ep ? a : ep;
@@ -239,98 +98,47 @@ __device__ inline void win_block_rmin2(int32_t& p, int32_t& q, int32_t none,
   *allq = aq;
 }
 
-__device__ inline int64_t win_load_int(const void* p, int64_t e, int32_t kind,
-                                       int32_t width) {
-  if (kind == WK_BOOL) return static_cast<const uint8_t*>(p)[e] != 0;
-  switch (width) {
-    case 1: return static_cast<const int8_t*>(p)[e];
-    case 2: return static_cast<const int16_t*>(p)[e];
-    case 4: return static_cast<const int32_t*>(p)[e];
-    default: return static_cast<const int64_t*>(p)[e];
-  }
-}
-
 // The scan input of function f at sorted position i (row `row`, -1 when perm
 // holds no row of the column there).
-__device__ inline WinState win_item(const WinFunc& f, int32_t op, int64_t i,
+__device__ inline SegState win_item(const SegFunc& f, int32_t op, int64_t i,
                                     int64_t row, bool part_head,
                                     bool peer_head) {
-  WinState x;
+  SegState x;
   x.flag = part_head;
   x.cnt = 0;
-  x.acc = win_identity(op);
+  x.acc = seg_identity(op);
   if (row < 0) return x;
   switch (f.fn) {
-    case WF_ROW_NUMBER:
+    case SF_ROW_NUMBER:
       x.cnt = 1;
       return x;
-    case WF_DENSE_RANK:
+    case SF_DENSE_RANK:
       x.cnt = peer_head;
       return x;
-    case WF_RANK:
+    case SF_RANK:
       x.cnt = 1;
       if (peer_head) x.acc = (uint64_t)i;
       return x;
     default:
-      break;
+      return seg_value_item(f, op, row, part_head);
   }
-  if (f.valid != nullptr && f.valid[row] == 0) return x;
-  x.cnt = 1;
-  if (op == OP_COUNT) return x;
-  const int64_t e = row * f.stride;
-  if (op == OP_SUM_I || op == OP_MIN_I || op == OP_MAX_I) {
-    x.acc = (uint64_t)win_load_int(f.values, e, f.kind, f.width);
-  } else {
-    double d;
-    if (f.kind == WK_F32) {
-      d = static_cast<const float*>(f.values)[e];
-    } else if (f.kind == WK_F64) {
-      d = static_cast<const double*>(f.values)[e];
-    } else {
-      d = (double)win_load_int(f.values, e, f.kind, f.width);
-    }
-    x.acc = win_bits(d);
-  }
-  return x;
 }
 
 // out[row] of function f from the state at the frame's last position.
-__device__ inline void win_store(const WinFunc& f, int64_t i, int64_t row,
+__device__ inline void win_store(const SegFunc& f, int64_t i, int64_t row,
                                  int64_t cnt, uint64_t acc) {
-  const bool has = cnt > 0;
   switch (f.fn) {
-    case WF_ROW_NUMBER:
-    case WF_DENSE_RANK:
-    case WF_COUNT:
+    case SF_ROW_NUMBER:
+    case SF_DENSE_RANK:
+    case SF_COUNT:
       static_cast<int64_t*>(f.out)[row] = cnt;
       return;
-    case WF_RANK:
+    case SF_RANK:
       static_cast<int64_t*>(f.out)[row] = cnt - i + (int64_t)acc;
       return;
-    case WF_SUM:
-      static_cast<uint64_t*>(f.out)[row] = has ? acc : 0ull;
-      break;
-    case WF_AVG:
-      static_cast<double*>(f.out)[row] =
-          has ? win_f64(acc) / (double)cnt : 0.0;
-      break;
-    default:  // min, max: the dtype of the input
-      if (f.kind == WK_F32) {
-        static_cast<float*>(f.out)[row] = has ? (float)win_f64(acc) : 0.0f;
-      } else if (f.kind == WK_F64) {
-        static_cast<uint64_t*>(f.out)[row] = has ? acc : 0ull;
-      } else {
-        const uint64_t v = has ? acc : 0ull;
-        switch (f.width) {
-          case 1: static_cast<uint8_t*>(f.out)[row] = (uint8_t)v; break;
-          case 2: static_cast<uint16_t*>(f.out)[row] = (uint16_t)v; break;
-          case 4: static_cast<uint32_t*>(f.out)[row] = (uint32_t)v; break;
-          default: static_cast<uint64_t*>(f.out)[row] = v; break;
-        }
-      }
-      break;
+    default:
+      seg_store_agg(f, row, cnt, acc);
   }
-  if (f.out_valid != nullptr) f.out_valid[row] = has ? 1 : 0;
 }
 
 __device__ inline int win_lds_slot(int p) { return p + (p >> 3); }
@@ -355,28 +163,28 @@ __host__ __device__ inline int64_t win_func_words(int64_t nt) {
 // EMIT = true: the small path (work == nullptr, one tile) and launch 3.
 template <bool EMIT>
 __global__ __launch_bounds__(DEFAULT_BLOCK) void window_tile_kernel(
-    WinFuncs fs, const int64_t* __restrict__ perm,
+    SegFuncs fs, const int64_t* __restrict__ perm,
     const uint8_t* __restrict__ part, const uint8_t* __restrict__ peer,
     int64_t m, int64_t nt, int64_t* work) {
   __shared__ int64_t s_cnt[WIN_SLOTS];   // 18 KiB
   __shared__ uint64_t s_acc[WIN_SLOTS];  // 18 KiB
-  __shared__ uint16_t s_np[WINDOW_TILE_ROWS];  // next partition head after p
-  __shared__ uint16_t s_nq[WINDOW_TILE_ROWS];  // next peer head after p
-  __shared__ WinState wt[WIN_WAVES];
-  __shared__ int32_t wm[2][WIN_WAVES];
+  __shared__ uint16_t s_np[SEG_TILE_ROWS];  // next partition head after p
+  __shared__ uint16_t s_nq[SEG_TILE_ROWS];  // next peer head after p
+  __shared__ SegState wt[SEG_WAVES];
+  __shared__ int32_t wm[2][SEG_WAVES];
   const int tid = threadIdx.x;
-  const int p0 = tid * WINDOW_EPT;
+  const int p0 = tid * SEG_EPT;
 
   for (int64_t T = blockIdx.x; T < nt; T += gridDim.x) {
-    const int64_t base = T * WINDOW_TILE_ROWS;
+    const int64_t base = T * SEG_TILE_ROWS;
     const int32_t nvalid =
-        m - base < WINDOW_TILE_ROWS ? (int32_t)(m - base) : WINDOW_TILE_ROWS;
+        m - base < SEG_TILE_ROWS ? (int32_t)(m - base) : SEG_TILE_ROWS;
     const bool last = T == nt - 1;
 
-    int64_t row[WINDOW_EPT];
+    int64_t row[SEG_EPT];
     uint32_t pf = 0, qf = 0;
 #pragma unroll
-    for (int k = 0; k < WINDOW_EPT; ++k) {
+    for (int k = 0; k < SEG_EPT; ++k) {
       const int64_t i = base + p0 + k;
       row[k] = -1;
       if (p0 + k < nvalid) {
@@ -395,7 +203,7 @@ __global__ __launch_bounds__(DEFAULT_BLOCK) void window_tile_kernel(
     int32_t firstp, firstq;  // first head of the tile
     win_block_rmin2(np, nq, WIN_NONE, wm, &firstp, &firstq);
 #pragma unroll
-    for (int k = WINDOW_EPT - 1; k >= 0; --k) {
+    for (int k = SEG_EPT - 1; k >= 0; --k) {
       // the last tile ends every frame at its last row
       s_np[p0 + k] = (uint16_t)((last && np > nvalid) ? nvalid : np);
       s_nq[p0 + k] = (uint16_t)((last && nq > nvalid) ? nvalid : nq);
@@ -417,31 +225,31 @@ __global__ __launch_bounds__(DEFAULT_BLOCK) void window_tile_kernel(
     __syncthreads();
 
     for (int32_t fi = 0; fi < fs.nf; ++fi) {
-      const WinFunc& f = fs.f[fi];
-      const int32_t op = win_op(f);
+      const SegFunc& f = fs.f[fi];
+      const int32_t op = seg_op(f);
       int64_t* fw =
           work != nullptr ? work + 4 * nt + fi * win_func_words(nt) : nullptr;
-      WinState carry;
+      SegState carry;
       carry.flag = 0;
       carry.cnt = 0;
-      carry.acc = win_identity(op);
+      carry.acc = seg_identity(op);
       if (EMIT && fw != nullptr) {
         carry.cnt = fw[2 * T];
         carry.acc = (uint64_t)fw[2 * T + 1];
       }
-      WinState s[WINDOW_EPT];
+      SegState s[SEG_EPT];
 #pragma unroll
-      for (int k = 0; k < WINDOW_EPT; ++k) {
-        const WinState x = win_item(f, op, base + p0 + k, row[k],
+      for (int k = 0; k < SEG_EPT; ++k) {
+        const SegState x = win_item(f, op, base + p0 + k, row[k],
                                     (pf >> k) & 1u, (qf >> k) & 1u);
-        s[k] = k == 0 ? x : win_combine(op, s[k - 1], x);
+        s[k] = k == 0 ? x : seg_combine(op, s[k - 1], x);
       }
-      WinState total;
-      const WinState pre =
-          win_block_scan(op, s[WINDOW_EPT - 1], carry, wt, &total);
+      SegState total;
+      const SegState pre =
+          seg_block_scan(op, s[SEG_EPT - 1], carry, wt, &total);
 #pragma unroll
-      for (int k = 0; k < WINDOW_EPT; ++k) {
-        s[k] = win_combine(op, pre, s[k]);
+      for (int k = 0; k < SEG_EPT; ++k) {
+        s[k] = seg_combine(op, pre, s[k]);
         const int slot = win_lds_slot(p0 + k);
         s_cnt[slot] = s[k].cnt;
         s_acc[slot] = s[k].acc;
@@ -449,33 +257,33 @@ __global__ __launch_bounds__(DEFAULT_BLOCK) void window_tile_kernel(
       __syncthreads();
 
       if (EMIT) {
-        const bool ranking = f.fn <= WF_DENSE_RANK;
-        const int32_t frame = ranking ? WFR_ROWS : f.frame;
+        const bool ranking = f.fn <= SF_DENSE_RANK;
+        const int32_t frame = ranking ? SFR_ROWS : f.frame;
         // frames that end past the tile: the closing state of the open
         // partition / peer group (the last tile has none)
         int64_t ecnt = 0;
         uint64_t eacc = 0;
-        if (fw != nullptr && !last && frame != WFR_ROWS) {
-          const int64_t nh = frame == WFR_PARTITION ? nhp : nhq;
+        if (fw != nullptr && !last && frame != SFR_ROWS) {
+          const int64_t nh = frame == SFR_PARTITION ? nhp : nhq;
           const int64_t* src =
               nh >= nt ? fw + 6 * nt
-                       : fw + (frame == WFR_PARTITION ? 2 : 4) * nt + 2 * nh;
+                       : fw + (frame == SFR_PARTITION ? 2 : 4) * nt + 2 * nh;
           ecnt = src[0];
           eacc = (uint64_t)src[1];
         }
 #pragma unroll
-        for (int k = 0; k < WINDOW_EPT; ++k) {
+        for (int k = 0; k < SEG_EPT; ++k) {
           if (row[k] < 0) continue;
           int64_t cnt = s[k].cnt;
           uint64_t acc = s[k].acc;
-          if (frame != WFR_ROWS) {
+          if (frame != SFR_ROWS) {
             const int32_t nx =
-                frame == WFR_PARTITION ? s_np[p0 + k] : s_nq[p0 + k];
+                frame == SFR_PARTITION ? s_np[p0 + k] : s_nq[p0 + k];
             if (!last && nx >= WIN_NONE) {
               cnt = ecnt;
               acc = eacc;
             } else {
-              // p0 + k < nx <= WINDOW_TILE_ROWS
+              // p0 + k < nx <= SEG_TILE_ROWS
               const int slot = win_lds_slot(nx - 1);
               cnt = s_cnt[slot];
               acc = s_acc[slot];
@@ -488,7 +296,7 @@ __global__ __launch_bounds__(DEFAULT_BLOCK) void window_tile_kernel(
         fw[2 * T] = s_cnt[lslot];
         fw[2 * T + 1] = (int64_t)s_acc[lslot];
         int64_t c = 0;
-        uint64_t a = win_identity(op);
+        uint64_t a = seg_identity(op);
         if (firstp > 0 && firstp < WIN_NONE) {
           c = s_cnt[win_lds_slot(firstp - 1)];
           a = s_acc[win_lds_slot(firstp - 1)];
@@ -496,7 +304,7 @@ __global__ __launch_bounds__(DEFAULT_BLOCK) void window_tile_kernel(
         fw[2 * nt + 2 * T] = c;
         fw[2 * nt + 2 * T + 1] = (int64_t)a;
         c = 0;
-        a = win_identity(op);
+        a = seg_identity(op);
         if (firstq > 0 && firstq < WIN_NONE) {
           c = s_cnt[win_lds_slot(firstq - 1)];
           a = s_acc[win_lds_slot(firstq - 1)];
@@ -511,11 +319,11 @@ __global__ __launch_bounds__(DEFAULT_BLOCK) void window_tile_kernel(
 
 // Launch 2 of the tiled path: one workgroup. See the work layout above.
 __global__ __launch_bounds__(DEFAULT_BLOCK) void window_carry_kernel(
-    WinFuncs fs, int64_t nt, int64_t* work) {
-  __shared__ WinState wt[WIN_WAVES];
-  __shared__ int32_t wm[2][WIN_WAVES];
+    SegFuncs fs, int64_t nt, int64_t* work) {
+  __shared__ SegState wt[SEG_WAVES];
+  __shared__ int32_t wm[2][SEG_WAVES];
   const int tid = threadIdx.x;
-  const int64_t nchunks = (nt + WINDOW_CARRY_CHUNK - 1) / WINDOW_CARRY_CHUNK;
+  const int64_t nchunks = (nt + SEG_CARRY_CHUNK - 1) / SEG_CARRY_CHUNK;
   const int32_t none = (int32_t)nt;  // nt < 2^31 (checked on the host)
   const int64_t* headp = work;
   const int64_t* headq = work + nt;
@@ -524,11 +332,11 @@ __global__ __launch_bounds__(DEFAULT_BLOCK) void window_carry_kernel(
   int32_t carryp = none, carryq = none;
   for (int64_t c = nchunks - 1; c >= 0; --c) {
     const int64_t t0 =
-        c * WINDOW_CARRY_CHUNK + (int64_t)tid * WINDOW_CARRY_PER_THREAD;
+        c * SEG_CARRY_CHUNK + (int64_t)tid * SEG_CARRY_PER_THREAD;
     uint32_t hp = 0, hq = 0;
     int32_t fp = none, fq = none;
 #pragma unroll
-    for (int k = WINDOW_CARRY_PER_THREAD - 1; k >= 0; --k) {
+    for (int k = SEG_CARRY_PER_THREAD - 1; k >= 0; --k) {
       const int64_t T = t0 + k;
       if (T < nt && headp[T] != 0) {
         hp |= 1u << k;
@@ -544,7 +352,7 @@ __global__ __launch_bounds__(DEFAULT_BLOCK) void window_carry_kernel(
     fp = carryp < fp ? carryp : fp;
     fq = carryq < fq ? carryq : fq;
 #pragma unroll
-    for (int k = WINDOW_CARRY_PER_THREAD - 1; k >= 0; --k) {
+    for (int k = SEG_CARRY_PER_THREAD - 1; k >= 0; --k) {
       const int64_t T = t0 + k;
       if (T < nt) {
         work[2 * nt + T] = fp;
@@ -559,65 +367,31 @@ __global__ __launch_bounds__(DEFAULT_BLOCK) void window_carry_kernel(
   }
 
   for (int32_t fi = 0; fi < fs.nf; ++fi) {
-    const int32_t op = win_op(fs.f[fi]);
+    const int32_t op = seg_op(fs.f[fi]);
     int64_t* fw = work + 4 * nt + fi * win_func_words(nt);
-    WinState carry;
-    carry.flag = 0;
-    carry.cnt = 0;
-    carry.acc = win_identity(op);
-    for (int64_t c = 0; c < nchunks; ++c) {
-      const int64_t t0 =
-          c * WINDOW_CARRY_CHUNK + (int64_t)tid * WINDOW_CARRY_PER_THREAD;
-      WinState s[WINDOW_CARRY_PER_THREAD];
+    const SegState end = seg_carry_scan(
+        op, headp, fw, nt, wt, [&](int64_t T, const SegState& ex) {
+          // the two prefix states of tile T close behind its carry-in
 #pragma unroll
-      for (int k = 0; k < WINDOW_CARRY_PER_THREAD; ++k) {
-        const int64_t T = t0 + k;
-        WinState x;
-        x.flag = 0;
-        x.cnt = 0;
-        x.acc = win_identity(op);
-        if (T < nt) {
-          x.flag = headp[T] != 0;
-          x.cnt = fw[2 * T];
-          x.acc = (uint64_t)fw[2 * T + 1];
-        }
-        s[k] = k == 0 ? x : win_combine(op, s[k - 1], x);
-      }
-      WinState total;
-      const WinState pre = win_block_scan(op, s[WINDOW_CARRY_PER_THREAD - 1],
-                                          carry, wt, &total);
-#pragma unroll
-      for (int k = 0; k < WINDOW_CARRY_PER_THREAD; ++k) {
-        const int64_t T = t0 + k;
-        if (T >= nt) continue;
-        // the state at the last row of tile T - 1
-        const WinState ex = k == 0 ? pre : win_combine(op, pre, s[k - 1]);
-#pragma unroll
-        for (int h = 2; h <= 4; h += 2) {
-          WinState px;
-          px.flag = 0;
-          px.cnt = fw[h * nt + 2 * T];
-          px.acc = (uint64_t)fw[h * nt + 2 * T + 1];
-          const WinState cl = win_combine(op, ex, px);
-          fw[h * nt + 2 * T] = cl.cnt;
-          fw[h * nt + 2 * T + 1] = (int64_t)cl.acc;
-        }
-        fw[2 * T] = ex.cnt;
-        fw[2 * T + 1] = (int64_t)ex.acc;
-      }
-      carry = total;
-      carry.flag = 0;
-      __syncthreads();  // wt is rewritten by the next chunk
-    }
+          for (int h = 2; h <= 4; h += 2) {
+            SegState px;
+            px.flag = 0;
+            px.cnt = fw[h * nt + 2 * T];
+            px.acc = (uint64_t)fw[h * nt + 2 * T + 1];
+            const SegState cl = seg_combine(op, ex, px);
+            fw[h * nt + 2 * T] = cl.cnt;
+            fw[h * nt + 2 * T + 1] = (int64_t)cl.acc;
+          }
+        });
     if (tid == 0) {
-      fw[6 * nt] = carry.cnt;
-      fw[6 * nt + 1] = (int64_t)carry.acc;
+      fw[6 * nt] = end.cnt;
+      fw[6 * nt + 1] = (int64_t)end.acc;
     }
   }
 }
 
 inline int64_t window_ntiles(int64_t m) {
-  return (m + WINDOW_TILE_ROWS - 1) / WINDOW_TILE_ROWS;
+  return (m + SEG_TILE_ROWS - 1) / SEG_TILE_ROWS;
 }
 
 }  // namespace srj
@@ -628,20 +402,20 @@ extern "C" {
 
 // bytes of scratch one srj_window call of nfuncs functions needs
 int64_t srj_window_work_bytes(int64_t m, int32_t nfuncs) {
-  if (m <= WINDOW_SMALL_ROWS) return 0;
+  if (m <= SEG_SMALL_ROWS) return 0;
   const int64_t nt = window_ntiles(m);
   return 8 * (4 * nt + (int64_t)nfuncs * win_func_words(nt));
 }
 
-// 1 <= nfuncs <= WINDOW_MAX_FUNCS, m > 0, peer may be null (every row its own
+// 1 <= nfuncs <= SEG_MAX_FUNCS, m > 0, peer may be null (every row its own
 // peer group), work: srj_window_work_bytes(m, nfuncs) bytes, 8-byte aligned.
-void srj_window(const WinFunc* funcs, int32_t nfuncs, const int64_t* perm,
+void srj_window(const SegFunc* funcs, int32_t nfuncs, const int64_t* perm,
                 const uint8_t* part, const uint8_t* peer, int64_t m,
                 int64_t* work, hipStream_t stream) {
-  WinFuncs a{};
+  SegFuncs a{};
   a.nf = nfuncs;
   for (int32_t i = 0; i < nfuncs; ++i) a.f[i] = funcs[i];
-  if (m <= WINDOW_SMALL_ROWS) {
+  if (m <= SEG_SMALL_ROWS) {
     window_tile_kernel<true><<<1, DEFAULT_BLOCK, 0, stream>>>(
         a, perm, part, peer, m, 1, nullptr);
     return;

@@ -733,6 +733,42 @@ def test_argument_validation():
             R(head, [good], perm.cuda())
 
 
+@pytest.mark.parametrize("fn", ["rank", "dense_rank"])
+def test_ranking_functions_are_unknown(fn):
+    """The window's ranking functions share the kernels' code table but are
+    no segmented reduce."""
+    head = torch.zeros(8, dtype=torch.bool)
+    with pytest.raises(ValueError, match="unknown function"):
+        SG.segmented_reduce_tensors(head, [(fn, None, None)])
+
+
+@pytest.mark.parametrize("code", [0, 1, 2])  # row_number, rank, dense_rank
+def test_binding_rejects_ranking_function_codes(code):
+    """The binding refuses a ranking code before anything is launched. Every
+    pointer is a real buffer of the 8-row call it describes."""
+    dev = "cuda" if torch.cuda.is_available() else "cpu"
+    m = 8
+    head = torch.zeros(m, dtype=torch.bool, device=dev)
+    v = torch.arange(m, dtype=torch.int64, device=dev)
+    ok = torch.ones(m, dtype=torch.bool, device=dev)
+    out = torch.full((m,), -7, dtype=torch.int64, device=dev)
+    ov = torch.zeros(m, dtype=torch.bool, device=dev)
+    first = torch.full((m,), -7, dtype=torch.int64, device=dev)
+    count = torch.full((1,), -7, dtype=torch.int64, device=dev)
+    g = _native.gpu()
+    assert g.seg_reduce_work_bytes(m, 1) == 0
+    desc = (code, 0, 2, 8, 1, v.data_ptr(), ok.data_ptr(), out.data_ptr(),
+            ov.data_ptr())
+    with pytest.raises(ValueError, match=r"seg_reduce: funcs\[0\]: unknown "
+                                         "function"):
+        g.seg_reduce([desc], 0, head.data_ptr(), m, m, m, first.data_ptr(),
+                     count.data_ptr(), 0, _native.current_stream()
+                     if dev == "cuda" else 0)
+    # nothing ran
+    assert out.tolist() == [-7] * m and first.tolist() == [-7] * m
+    assert count.tolist() == [-7]
+
+
 # ---------------------------------------------------------------------------
 # GPU tier
 # ---------------------------------------------------------------------------
