@@ -422,6 +422,53 @@ def join_narrow_bench(nb, npr, iters, dev, g):
     tables.clear()
 
 
+def join_dense_bench(nb, npr, iters, dev, g):
+    """Dense (direct-address) against narrow (8-byte hashed slot) join table,
+    both forced, on the same duplicate-free int64 keys, sorted and shuffled;
+    build and probe timed separately and alternating. The build time includes
+    the zero fill, the min/max scan with its read-back and, for dense, the
+    read-back of the duplicate flag."""
+    from spark_rapids_jni_amd.columnar import Column, DType
+    from spark_rapids_jni_amd.ops.join import HashJoinTable
+    keys = torch.arange(nb, dtype=torch.int64, device=dev)
+    pcol = Column(DType.INT64, npr, torch.randint(
+        0, 2 * nb, (npr,), dtype=torch.int64, device=dev, generator=g))
+    kw = {"dense": {"dense": True}, "narrow": {"narrow": True}}
+    for order in ("sorted", "shuffled"):
+        if order == "shuffled":
+            keys = keys[torch.randperm(nb, device=dev, generator=g)]
+        bcol = Column(DType.INT64, nb, keys)
+        tables = {}
+
+        def build(path):
+            def run():
+                tables[path] = None  # one table resident at a time
+                tables[path] = HashJoinTable.build(bcol, **kw[path])
+            return run
+
+        def probe(path):
+            return lambda: tables[path].inner_join(pcol, out_hint=npr)
+
+        for phase, fn in (("build", build), ("probe", probe)):
+            rows = nb if phase == "build" else npr
+            if phase == "probe":
+                for path in kw:
+                    tables[path] = HashJoinTable.build(bcol, **kw[path])
+                assert tables["dense"].layout == "dense"
+                assert tables["narrow"].layout == "narrow"
+            den, nar = ab_time(fn("dense"), fn("narrow"), iters, repeats=3)
+            for path, xs in (("dense", den), ("narrow", nar)):
+                xs = sorted(xs)
+                print(json.dumps({
+                    "bench": f"join_dense_{phase}", "path": path,
+                    "keys": order, "build_rows": nb, "probe_rows": npr,
+                    "ms": round(xs[1] * 1e3, 4),
+                    "ms_min": round(xs[0] * 1e3, 4),
+                    "ms_max": round(xs[2] * 1e3, 4),
+                    "rows_per_sec": round(rows / xs[1], 1)}), flush=True)
+        tables.clear()
+
+
 def plumbing_bench():
     """BASELINE config[0]: murmur3 + row<->columnar on a 1k-row int64 batch
     via the HOST path (no GPU) — measures binding/plumbing overhead like the
@@ -452,8 +499,9 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=2**24)
     ap.add_argument("--iters", type=int, default=5)
-    ap.add_argument("--only", choices=["sort_order", "join_narrow", "window",
-                                      "expr", "groupby_sorted"],
+    ap.add_argument("--only", choices=["sort_order", "join_narrow",
+                                      "join_dense", "window", "expr",
+                                      "groupby_sorted"],
                     default=None,
                     help="run just this group")
     args = ap.parse_args()
@@ -487,6 +535,13 @@ def main():
         # beyond the Infinity Cache, then cache resident
         for nb, npr in ((2**26, 2**26), (2**20, 2**24)):
             join_narrow_bench(nb, npr, args.iters, "cuda", g)
+        return
+    if args.only == "join_dense":
+        g = torch.Generator(device="cuda")
+        g.manual_seed(7)
+        # beyond the Infinity Cache, then cache resident
+        for nb, npr in ((2**26, 2**26), (2**20, 2**24)):
+            join_dense_bench(nb, npr, args.iters, "cuda", g)
         return
     plumbing_bench()  # CPU shape (BASELINE config[0]) first
     n = args.rows

@@ -64,6 +64,15 @@ NARROW_SCAN_MIN_ROWS = 1 << 22
 # slots per build row before rounding up to a power of two (25% max load)
 NARROW_SLOTS_PER_ROW = 4
 _I32_KMIN = -(1 << 31)
+# a key range of at most this many slots per build row takes the direct-
+# address table: at most 8 B per build row, a quarter of the narrow table
+DENSE_MAX_SLOTS_PER_ROW = 2
+
+
+def _is_dense(lo: int, hi: int, n: int) -> bool:
+    """True when the key range [lo, hi] of n build rows is small enough for
+    one direct-address slot per key of the range."""
+    return hi - lo + 1 <= max(DENSE_MAX_SLOTS_PER_ROW * n, 64)
 
 
 def _fits_narrow(lo: int, hi: int) -> bool:
@@ -147,13 +156,18 @@ class HashJoinTable:
     """Build-side hash table reusable across probes (reference: the build/probe
     split of hash_inner_join).
 
-    Three layouts (`layout`): "generic", a (fingerprint32|row+1) single-word
+    Four layouts (`layout`): "generic", a (fingerprint32|row+1) single-word
     table for any key schema; "wide", the specialized 16-byte {key,row} table
-    for single integer keys that need 64 bits; and "narrow", one 8-byte word
+    for single integer keys that need 64 bits; "narrow", one 8-byte word
     (key - kmin | row+1 | chain) per slot for keys whose range fits 32 bits —
-    INT32/DATE32 columns, packed tuples, dense int64 surrogate keys. Wide and
-    narrow are the software-pipelined fast path (`i64_fast`), see
-    src/gpu/hashtable_i64.hip. `capacity` is the slot count in every layout.
+    INT32/DATE32 columns, packed tuples, int64 surrogate keys; and "dense",
+    a direct-address table of one 4-byte word (row+1) per key of
+    [kmin, kmin + capacity) with no hashing at all, for a single integer key
+    column that is duplicate-free and whose range is at most
+    DENSE_MAX_SLOTS_PER_ROW slots per row (src/gpu/join_dense.hip). Wide,
+    narrow and dense are the software-pipelined fast path (`i64_fast`), see
+    src/gpu/hashtable_i64.hip. `capacity` is the slot count in every layout;
+    it is a power of two except for dense, where it is the key range.
     """
 
     def __init__(self, build_keys: List[Column], slots: torch.Tensor,
@@ -171,11 +185,22 @@ class HashJoinTable:
     @staticmethod
     def build(keys: Union[Column, Table, Sequence[Column]],
               force_generic: bool = False,
-              narrow: Optional[bool] = None) -> "HashJoinTable":
+              narrow: Optional[bool] = None,
+              dense: Optional[bool] = None) -> "HashJoinTable":
         """narrow: True forces the 8-byte-slot table (raises if the key range
-        does not fit 32 bits), False forbids it, None decides: 4-byte-or-less
-        key columns and packed tuples of width product <= 2^32 always, int64
-        columns from NARROW_SCAN_MIN_ROWS rows when a min/max scan fits."""
+        does not fit 32 bits), False forbids it (wide), None decides:
+        4-byte-or-less key columns and packed tuples of width product <= 2^32
+        always, int64 columns from NARROW_SCAN_MIN_ROWS rows when a min/max
+        scan fits. Neither True nor False ever gives the dense table.
+
+        dense: True forces the direct-address table for a single integer key
+        column of any width and row count (scans the range; raises if it is
+        not dense or a key repeats), False forbids it. None applies only where
+        narrow is None and an int64 column is range-scanned anyway: a dense
+        range builds the direct table and reads back its duplicate flag (one
+        more read-back; the probe cannot start before the build ends); if a
+        key repeats the table is dropped and the narrow build goes ahead with
+        the range already known."""
         cols = _keys(keys)
         n = cols[0].size
         assert n < 2**31, "build side capped at 2^31-1 rows (chunk the build)"
@@ -196,6 +221,36 @@ class HashJoinTable:
             tbl = HashJoinTable(cols, slots, cap, keep, True, "narrow", kmin)
             if pack is not None:
                 tbl._pack = pack
+            return tbl
+
+        def build_dense(data, key_i32, valid, lo, hi):
+            """The direct-address table over [lo, hi], or None when a build
+            key repeats (the table cannot hold it)."""
+            span = hi - lo + 1
+            slots = torch.zeros(span, dtype=torch.int32, device=dev)
+            flag = torch.zeros(1, dtype=torch.int32, device=dev)
+            g.join_build_d32(data.data_ptr(), key_i32,
+                             valid.data_ptr() if valid is not None else 0,
+                             n, slots.data_ptr(), span, lo, flag.data_ptr(),
+                             stream)
+            bad = int(flag.item())
+            assert not bad & 2, "build key outside its scanned range"
+            if bad:
+                return None
+            return HashJoinTable(cols, slots, span, None, True, "dense", lo)
+
+        if dense:
+            if force_generic or narrow is not None or not _is_i64_fast(cols):
+                raise ValueError("dense=True needs a single integer key "
+                                 "column and no other layout forced")
+            data, key_i32 = _narrow_keys(cols[0])
+            lo, hi = _key_range(data) if n else (0, 0)
+            if not _is_dense(lo, hi, n):
+                raise ValueError(f"dense=True: key range [{lo}, {hi}] is not "
+                                 f"dense for {n} rows")
+            tbl = build_dense(data, key_i32, cols[0].validity, lo, hi)
+            if tbl is None:
+                raise ValueError("dense=True: duplicate build key")
             return tbl
 
         pack = None
@@ -231,6 +286,11 @@ class HashJoinTable:
                                         data)
                 if narrow or n >= NARROW_SCAN_MIN_ROWS:
                     lo, hi = _key_range(c0.data) if n else (0, 0)
+                    if (narrow is None and dense is None
+                            and _is_dense(lo, hi, n)):
+                        tbl = build_dense(c0.data, 0, c0.validity, lo, hi)
+                        if tbl is not None:
+                            return tbl
                     if _fits_narrow(lo, hi):
                         return build_narrow(c0.data, 0, c0.validity, lo, None)
                     if narrow:
@@ -271,7 +331,7 @@ class HashJoinTable:
                           null_count=None)
         if not _is_i64_fast(pcols):
             return None
-        if self.layout == "narrow":
+        if self.layout in ("narrow", "dense"):
             return pcols[0]  # read in place, whatever its integer width
         return _as_i64_keys(pcols[0])
 
@@ -279,7 +339,13 @@ class HashJoinTable:
                     out_capacity, matched, fill, stream):
         g = _native.gpu()
         pvalid = p.validity.data_ptr() if p.validity is not None else 0
-        if self.layout == "narrow":
+        if self.layout == "dense":
+            data, key_i32 = _narrow_keys(p)
+            g.join_probe_d32(data.data_ptr(), key_i32, pvalid, p.size,
+                             self.slots.data_ptr(), self.capacity, self.kmin,
+                             counter.data_ptr(), out_build, out_probe,
+                             out_capacity, matched, fill, stream)
+        elif self.layout == "narrow":
             data, key_i32 = _narrow_keys(p)
             g.join_probe_n32(data.data_ptr(), key_i32, pvalid, p.size,
                              self.slots.data_ptr(), self.capacity, self.kmin,
@@ -383,18 +449,21 @@ class HashJoinTable:
             # semi/anti runs on the generic slot layout
             if not hasattr(self, "_generic"):
                 g = _native.gpu()
-                n = self.build_keys[0].size
-                slots = torch.zeros(self.capacity, dtype=torch.int64,
+                n = self.num_build_rows
+                # the generic table's own size (50% max load), not
+                # self.capacity: a dense table's is no power of two
+                capacity = max(_next_pow2(2 * n), 64)
+                slots = torch.zeros(capacity, dtype=torch.int64,
                                     device=self.build_keys[0].device)
                 desc, top, keep = pack_descriptors(self.build_keys)
                 # hash over ALL key columns — a single-column hash here
                 # silently misses every multi-key match (r2 fix)
                 g.join_build(desc.data_ptr(), top.data_ptr(),
                              len(self.build_keys), n,
-                             slots.data_ptr(), self.capacity,
+                             slots.data_ptr(), capacity,
                              _native.current_stream())
                 self._generic = HashJoinTable(self.build_keys, slots,
-                                              self.capacity, (desc, top, keep),
+                                              capacity, (desc, top, keep),
                                               False)
             return self._generic.semi_join(probe, anti)
         pcols = _keys(probe)

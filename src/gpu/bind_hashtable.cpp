@@ -44,6 +44,11 @@ void srj_join_probe_n32(const void*, int32_t, const uint8_t*, int64_t,
                         const void*, int64_t, long long, uint64_t*, int32_t*,
                         int64_t*, int64_t, uint8_t*, int32_t, const int32_t*,
                         hipStream_t);
+void srj_join_build_d32(const void*, int32_t, const uint8_t*, int64_t, void*,
+                        int64_t, long long, uint32_t*, hipStream_t);
+void srj_join_probe_d32(const void*, int32_t, const uint8_t*, int64_t,
+                        const void*, int64_t, long long, uint64_t*, int32_t*,
+                        int64_t*, int64_t, uint8_t*, int32_t, hipStream_t);
 }
 
 void register_hashtable(py::module_& m) {
@@ -184,6 +189,30 @@ void register_hashtable(py::module_& m) {
                              as_ptr<uint8_t>(build_matched), fill,
                              as_ptr<int32_t>(idxmap), as_stream(stream));
           check_hip("join_probe_n32");
+        });
+  m.def("join_build_d32",
+        [](uintptr_t keys, int32_t key_i32, uintptr_t valid, int64_t nrows,
+           uintptr_t slots, int64_t range, int64_t kmin, uintptr_t flag,
+           uintptr_t stream) {
+          srj_join_build_d32(as_ptr<void>(keys), key_i32, as_ptr<uint8_t>(valid),
+                             nrows, as_ptr<void>(slots), range, (long long)kmin,
+                             as_ptr<uint32_t>(flag), as_stream(stream));
+          check_hip("join_build_d32");
+        });
+  m.def("join_probe_d32",
+        [](uintptr_t probe, int32_t key_i32, uintptr_t pvalid, int64_t nprobe,
+           uintptr_t slots, int64_t range, int64_t kmin, uintptr_t counter,
+           uintptr_t out_build, uintptr_t out_probe, int64_t out_capacity,
+           uintptr_t build_matched, int32_t fill, uintptr_t stream) {
+          srj_join_probe_d32(as_ptr<void>(probe), key_i32,
+                             as_ptr<uint8_t>(pvalid), nprobe,
+                             as_ptr<void>(slots), range, (long long)kmin,
+                             as_ptr<uint64_t>(counter),
+                             as_ptr<int32_t>(out_build),
+                             as_ptr<int64_t>(out_probe), out_capacity,
+                             as_ptr<uint8_t>(build_matched), fill,
+                             as_stream(stream));
+          check_hip("join_probe_d32");
         });
   m.def("part_hist",
         [](uintptr_t keys, int64_t n, int32_t pbits, uintptr_t hist,
