@@ -164,10 +164,11 @@ class HashJoinTable:
     a direct-address table of one 4-byte word (row+1) per key of
     [kmin, kmin + capacity) with no hashing at all, for a single integer key
     column that is duplicate-free and whose range is at most
-    DENSE_MAX_SLOTS_PER_ROW slots per row (src/gpu/join_dense.hip). Wide,
-    narrow and dense are the software-pipelined fast path (`i64_fast`), see
-    src/gpu/hashtable_i64.hip. `capacity` is the slot count in every layout;
-    it is a power of two except for dense, where it is the key range.
+    DENSE_MAX_SLOTS_PER_ROW slots per row. Wide, narrow and dense are the
+    software-pipelined fast path (`i64_fast`), see src/gpu/join_fast.hip and
+    its one probe kernel, src/gpu/join_probe.hpp. `capacity` is the slot
+    count in every layout; it is a power of two except for dense, where it is
+    the key range.
     """
 
     def __init__(self, build_keys: List[Column], slots: torch.Tensor,

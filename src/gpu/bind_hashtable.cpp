@@ -29,9 +29,6 @@ void srj_groupby_compact_i64_count(const void*, int64_t, int64_t*,
 void srj_groupby_compact_i64_fill(const void*, int64_t, const void*, int32_t,
                                   const int64_t*, int64_t*, int64_t*, int64_t,
                                   hipStream_t);
-void srj_groupby_compact_i64(const void*, int64_t, const void*, int32_t,
-                             uint64_t*, int64_t*, int64_t*, int64_t,
-                             hipStream_t);
 void srj_part_hist(const long long*, int64_t, int32_t, int64_t*, hipStream_t);
 void srj_part_scatter(const long long*, int64_t, int32_t, int64_t*, long long*,
                       int32_t*, hipStream_t);
@@ -120,18 +117,6 @@ void register_hashtable(py::module_& m) {
                               as_ptr<int64_t>(identities),
                               as_ptr<int32_t>(overflow), as_stream(stream));
           check_hip("groupby_i64_lds");
-        });
-  m.def("groupby_compact_i64",
-        [](uintptr_t slots, int64_t capacity1, uintptr_t aggs, int32_t naggs,
-           uintptr_t counter, uintptr_t out_repr, uintptr_t out_agg,
-           int64_t out_capacity, uintptr_t stream) {
-          srj_groupby_compact_i64(as_ptr<void>(slots), capacity1,
-                                  as_ptr<void>(aggs), naggs,
-                                  as_ptr<uint64_t>(counter),
-                                  as_ptr<int64_t>(out_repr),
-                                  as_ptr<int64_t>(out_agg), out_capacity,
-                                  as_stream(stream));
-          check_hip("groupby_compact_i64");
         });
   m.def("groupby_compact_i64_count",
         [](uintptr_t slots, int64_t capacity1, uintptr_t blk_counts,

@@ -55,7 +55,7 @@ __global__ void join_build_kernel(const ColDesc* __restrict__ cols,
 // probe: two-phase (count then fill). COUNT uses one wave-level reduction +
 // a single atomicAdd per wave. FILL appends match pairs at a global cursor.
 // ---------------------------------------------------------------------------
-constexpr int GPIPE = 8;  // probe rows in flight per lane (as hashtable_i64)
+constexpr int GPIPE = 8;  // probe rows in flight per lane (as join_probe.hpp)
 
 template <bool FILL>
 __global__ void join_probe_kernel(
@@ -68,7 +68,7 @@ __global__ void join_probe_kernel(
   // software-pipelined batches: hashes and first slot words for GPIPE rows
   // are issued before any chain resolves (the slot-word loads are THE
   // random accesses this kernel is bound by; same structure as the int64
-  // fast path in hashtable_i64.hip)
+  // fast path in join_probe.hpp)
   int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   int64_t nthreads = (int64_t)gridDim.x * blockDim.x;
   uint64_t local = 0;

@@ -1,0 +1,412 @@
+// The join fast path (single integer key; the NDS hot path: fact-table joins
+// on surrogate keys, BASELINE config[2]): three table layouts, a build kernel
+// each, and one probe pipeline over all of them (join_probe.hpp).
+//
+// Why a separate design from hashtable.hip's generic (fp|row) table: the
+// generic probe is a dependent chain of TWO random loads per row (slot word,
+// then the build key for equality). rocprof on the v1 kernel showed it
+// latency-bound at ~3% of HBM bandwidth (profiles/r01_join_v1_kernel_stats).
+// Here the key is inline in the slot, so a probe is ONE random load per slot
+// visited, and builds and probes are software-pipelined batches of PIPE rows
+// per lane: first-slot accesses for the whole batch issue independently
+// before any is resolved (memory-level parallelism instead of one dependent
+// chain).
+//
+//   wide    16-byte {key, row+1} slots, any int64 key
+//   narrow  8-byte key-kmin | row+1 | chain words, key range within 32 bits
+//   dense   4-byte row+1 words addressed by key-kmin, no hashing, for a
+//           duplicate-free key column of a dense range
+#include "i64_slots.hpp"
+#include "join_probe.hpp"
+
+namespace srj {
+
+// ---------------------------------------------------------------------------
+// wide table. Claim protocol: atomicCAS on the row word (0 = empty), winner
+// writes key; no sentinel key needed, build completes before probe launches.
+// ---------------------------------------------------------------------------
+__global__ void join_build_i64_kernel(const long long* __restrict__ keys,
+                                      const uint8_t* __restrict__ valid,
+                                      int64_t nrows, Slot64* __restrict__ slots,
+                                      uint64_t mask) {
+  int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  int64_t nthreads = (int64_t)gridDim.x * blockDim.x;
+  // batch of PIPE strided rows per iteration
+  for (int64_t base = tid * PIPE; base < nrows; base += nthreads * PIPE) {
+    long long k[PIPE];
+    uint64_t s[PIPE];
+    bool act[PIPE];
+    long long prev[PIPE];
+#pragma unroll
+    for (int b = 0; b < PIPE; ++b) {
+      int64_t row = base + b;
+      act[b] = row < nrows && is_valid(valid, row);
+      k[b] = act[b] ? keys[row < nrows ? row : 0] : 0;
+      s[b] = act[b] ? slot_of(i64_hash(k[b]), mask) : 0;
+    }
+    // first-slot claims issued back-to-back (independent atomics pipeline
+    // with counted vmcnt); inactive lanes CAS 0->0 on slot 0, a no-op
+#pragma unroll
+    for (int b = 0; b < PIPE; ++b) {
+      prev[b] = atomicCAS(
+          reinterpret_cast<unsigned long long*>(&slots[s[b]].row1), 0ull,
+          (unsigned long long)(act[b] ? base + b + 1 : 0));
+    }
+#pragma unroll
+    for (int b = 0; b < PIPE; ++b) {
+      if (!act[b]) continue;
+      if (prev[b] == 0) {
+        slots[s[b]].key = k[b];
+        continue;
+      }
+      int64_t row = base + b;
+      // mark the displaced-over slots so probes know the chain continues
+      atomicOr(reinterpret_cast<unsigned long long*>(&slots[s[b]].row1),
+               (unsigned long long)SLOT_CHAIN);
+      uint64_t sl = (s[b] + 1) & mask;
+      while (true) {
+        long long p = atomicCAS(
+            reinterpret_cast<unsigned long long*>(&slots[sl].row1), 0ull,
+            (unsigned long long)(row + 1));
+        if (p == 0) {
+          slots[sl].key = k[b];
+          break;
+        }
+        atomicOr(reinterpret_cast<unsigned long long*>(&slots[sl].row1),
+                 (unsigned long long)SLOT_CHAIN);
+        sl = (sl + 1) & mask;
+      }
+    }
+  }
+}
+
+struct WideLayout {
+  using Tag = long long;  // the key itself
+  using Word = longlong2;  // {key, row1} in one load
+  using Index = uint64_t;
+  static constexpr bool CHAINED = true;
+  static constexpr bool PLAIN_BATCH = false;
+  const longlong2* slots;
+  uint64_t mask;
+
+  __device__ Index index(long long key, Tag& tag, bool& live) const {
+    tag = key;
+    live = true;
+    return slot_of(i64_hash(key), mask);
+  }
+  __device__ Index reindex(Tag tag) const {
+    return slot_of(i64_hash(tag), mask);
+  }
+  __device__ Index next(Index i) const { return (i + 1) & mask; }
+  __device__ Word load(Index i) const { return slots[i]; }
+  __device__ static bool empty(Word w) { return w.y == 0; }
+  __device__ static bool match(Word w, Tag tag) { return w.x == tag; }
+  __device__ static bool chain(Word w) { return w.y & SLOT_CHAIN; }
+  // the build side is capped below 2^31 rows
+  __device__ static uint32_t row1(Word w) { return (uint32_t)(w.y & SLOT_ROW); }
+};
+
+// ---------------------------------------------------------------------------
+// narrow table: 8-byte slots for keys whose range fits 32 bits (INT32/DATE32
+// columns, packed multi-key tuples, int64 surrogate keys of a dense range).
+//   word = (key - kmin) | (row + 1) << 32 | chain << 63;   0 = empty
+// One CAS 0 -> word claims the slot and publishes key and row together, so an
+// insert is one memory-side transaction instead of a CAS plus a scattered
+// key store, and the table is half the bytes at the same load. The slot index
+// still comes from the hash of the ORIGINAL key (part_hist / part_scatter
+// prefixes line up with table windows exactly as for the wide table).
+// K is the key column's element type: int columns are read in place.
+// ---------------------------------------------------------------------------
+constexpr unsigned long long NSLOT_CHAIN = 1ull << 63;
+constexpr uint32_t NSLOT_ROW = 0x7fffffffu;  // of the word's high half
+
+template <typename K>
+__global__ void join_build_n32_kernel(const K* __restrict__ keys,
+                                      const uint8_t* __restrict__ valid,
+                                      int64_t nrows,
+                                      unsigned long long* __restrict__ slots,
+                                      uint64_t mask, long long kmin) {
+  int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  int64_t nthreads = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t base = tid * PIPE; base < nrows; base += nthreads * PIPE) {
+    unsigned long long w[PIPE];
+    uint64_t s[PIPE];
+    unsigned long long prev[PIPE];
+#pragma unroll
+    for (int b = 0; b < PIPE; ++b) {
+      int64_t row = base + b;
+      bool act = row < nrows && is_valid(valid, row);
+      long long k = act ? (long long)keys[row] : 0;
+      // the host guarantees key - kmin < 2^32 for every valid build row
+      w[b] = act ? ((uint64_t)(uint32_t)((uint64_t)k - (uint64_t)kmin) |
+                    (uint64_t)(row + 1) << 32)
+                 : 0ull;
+      s[b] = act ? slot_of(i64_hash(k), mask) : 0;
+    }
+    // first-slot claims back-to-back; inactive lanes CAS 0->0 on slot 0
+#pragma unroll
+    for (int b = 0; b < PIPE; ++b) prev[b] = atomicCAS(&slots[s[b]], 0ull, w[b]);
+#pragma unroll
+    for (int b = 0; b < PIPE; ++b) {
+      if (w[b] == 0 || prev[b] == 0) continue;
+      // mark the displaced-over slots so probes know the chain continues
+      atomicOr(&slots[s[b]], NSLOT_CHAIN);
+      uint64_t sl = (s[b] + 1) & mask;
+      while (atomicCAS(&slots[sl], 0ull, w[b]) != 0) {
+        atomicOr(&slots[sl], NSLOT_CHAIN);
+        sl = (sl + 1) & mask;
+      }
+    }
+  }
+}
+
+// A lane keeps only the 32-bit key offset and the fetched word per row, which
+// keeps the batch state small enough for a fifth wave per SIMD.
+struct NarrowLayout {
+  using Tag = uint32_t;  // key - kmin
+  using Word = unsigned long long;
+  using Index = uint64_t;
+  static constexpr bool CHAINED = true;
+  static constexpr bool PLAIN_BATCH = false;
+  const unsigned long long* slots;
+  uint64_t mask;
+  long long kmin;
+
+  __device__ Index index(long long key, Tag& tag, bool& live) const {
+    uint64_t o = (uint64_t)key - (uint64_t)kmin;
+    tag = (uint32_t)o;
+    // an offset past 32 bits can never match; it must not alias
+    live = !(o >> 32);
+    return slot_of(i64_hash(key), mask);
+  }
+  __device__ Index reindex(Tag tag) const {
+    return slot_of(i64_hash((long long)((uint64_t)kmin + (uint64_t)tag)), mask);
+  }
+  __device__ Index next(Index i) const { return (i + 1) & mask; }
+  __device__ Word load(Index i) const { return slots[i]; }
+  __device__ static bool empty(Word w) { return w == 0; }
+  __device__ static bool match(Word w, Tag tag) { return (uint32_t)w == tag; }
+  __device__ static bool chain(Word w) { return w & NSLOT_CHAIN; }
+  __device__ static uint32_t row1(Word w) {
+    return (uint32_t)(w >> 32) & NSLOT_ROW;
+  }
+};
+
+// ---------------------------------------------------------------------------
+// dense table: direct addressing for dense, duplicate-free integer build keys
+// (the shape of nearly every NDS surrogate key: d_date_sk, i_item_sk, ...).
+//   slots[key - kmin] = row + 1;   0 = empty;   one uint32 per key of
+//   [kmin, kmin + range)
+// Hashing is work such a join does not need: the table is range x 4 B (an
+// eighth of the narrow table at 25 % load), a build is one CAS per row with
+// no chain, and a probe is one 4-byte load per row with at most one match. A
+// duplicate build key cannot be represented: the build raises a flag and the
+// host falls back to the hashed tables.
+// ---------------------------------------------------------------------------
+constexpr int DPIPE = 8;  // build rows per lane and iteration
+
+// Rows of a wave are interleaved (row = wave base + b * 64 + lane), not
+// consecutive per lane: for sorted keys the 64 claims of one atomic
+// instruction are then one contiguous 256-byte segment, the shape memory-side
+// atomics run at full rate for, and the key loads are fully coalesced.
+// Keys and validity bytes load unconditionally (clamped) and every lane
+// issues its DPIPE claims back-to-back: a row that is null or past the end
+// issues CAS 0 -> 0, a no-op on whatever slot it lands on, spread over the
+// table's first 64 slots so that nulls do not pile onto one address.
+// flag (one word, ordinary stores): bit 0 = duplicate key, bit 1 = a key
+// outside [kmin, kmin + range), which the host rules out; such a row is
+// dropped, never stored out of bounds.
+template <typename K>
+__global__ void join_build_d32_kernel(const K* __restrict__ keys,
+                                      const uint8_t* __restrict__ valid,
+                                      int64_t nrows,
+                                      uint32_t* __restrict__ slots,
+                                      uint64_t range, long long kmin,
+                                      uint32_t* __restrict__ flag) {
+  int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  int64_t nwaves = (int64_t)gridDim.x * blockDim.x / WAVE;
+  uint32_t lane = threadIdx.x & (WAVE - 1);
+  uint32_t idle = lane < range ? lane : 0u;  // slot of this lane's no-op CAS
+  constexpr int64_t WROWS = (int64_t)WAVE * DPIPE;
+  uint32_t bad = 0;
+  for (int64_t base = (tid / WAVE) * WROWS; base < nrows;
+       base += nwaves * WROWS) {
+    long long k[DPIPE];
+    uint32_t vb[DPIPE];
+    uint32_t o[DPIPE], w[DPIPE], prev[DPIPE];
+#pragma unroll
+    for (int b = 0; b < DPIPE; ++b) {
+      int64_t row = base + (int64_t)b * WAVE + lane;
+      int64_t crow = row < nrows ? row : 0;
+      k[b] = (long long)keys[crow];
+      vb[b] = valid ? (uint32_t)valid[crow >> 3] : 0xffu;
+    }
+#pragma unroll
+    for (int b = 0; b < DPIPE; ++b) {
+      int64_t row = base + (int64_t)b * WAVE + lane;
+      bool act = row < nrows && ((vb[b] >> (row & 7)) & 1);
+      uint64_t off = (uint64_t)k[b] - (uint64_t)kmin;
+      if (act && off >= range) {
+        bad |= 2u;
+        act = false;
+      }
+      o[b] = act ? (uint32_t)off : idle;
+      w[b] = act ? (uint32_t)(row + 1) : 0u;
+    }
+#pragma unroll
+    for (int b = 0; b < DPIPE; ++b) prev[b] = atomicCAS(&slots[o[b]], 0u, w[b]);
+    // a failed claim of a live row is a duplicate key: no chain, no retry
+#pragma unroll
+    for (int b = 0; b < DPIPE; ++b)
+      if (w[b] != 0 && prev[b] != 0) bad |= 1u;
+  }
+  if (bad) atomicOr(flag, bad);
+}
+
+// A key is live when key - kmin, compared as a full 64-bit value, is below
+// range; a dead row loads slot 0, so no load leaves the table and an offset
+// that wraps past 2^32 or 2^63 cannot alias.
+struct DenseLayout {
+  struct Tag {};  // the slot index is the whole comparison
+  using Word = uint32_t;
+  using Index = uint32_t;
+  static constexpr bool CHAINED = false;
+  static constexpr bool PLAIN_BATCH = true;
+  const uint32_t* slots;
+  uint64_t range;
+  long long kmin;
+
+  __device__ Index index(long long key, Tag&, bool& live) const {
+    uint64_t o = (uint64_t)key - (uint64_t)kmin;
+    live = o < range;
+    return live ? (uint32_t)o : 0u;
+  }
+  __device__ Word load(Index i) const { return slots[i]; }
+  __device__ static bool empty(Word w) { return w == 0; }
+  __device__ static bool match(Word, Tag) { return true; }
+  __device__ static uint32_t row1(Word w) { return w; }
+};
+
+// Dense probe rows per lane and batch, chosen by measurement (docs/PERF.md):
+// 16 while the table fits the 256 MiB Infinity Cache (half the wave-wide
+// appends, 1.7x the probe rate at 2^20 and 2^26 slots), 8 beyond it, where
+// the probe lives on waves in flight (29.1 against 31.4 ms per 1B rows into
+// 1B slots).
+constexpr uint64_t DENSE_PIPE16_MAX_SLOTS = 1ull << 26;
+
+}  // namespace srj
+
+using namespace srj;
+
+extern "C" {
+
+void srj_join_build_i64(const long long* keys, const uint8_t* valid, int64_t nrows,
+                        void* slots, int64_t capacity, hipStream_t stream) {
+  int64_t nthreads_needed = (nrows + PIPE - 1) / PIPE;
+  join_build_i64_kernel<<<grid_1d(nthreads_needed), DEFAULT_BLOCK, 0, stream>>>(
+      keys, valid, nrows, reinterpret_cast<Slot64*>(slots),
+      (uint64_t)(capacity - 1));
+}
+
+// batch 16 measured slower for the wide table (12.5 vs 15.8 B rows/s):
+// occupancy drop
+void srj_join_probe_i64(const long long* probe, const uint8_t* pvalid,
+                        int64_t nprobe, const void* slots, int64_t capacity,
+                        uint64_t* counter, int32_t* out_build, int64_t* out_probe,
+                        int64_t out_capacity, uint8_t* build_matched, int32_t fill,
+                        const int32_t* idxmap, hipStream_t stream) {
+  WideLayout l{reinterpret_cast<const longlong2*>(slots),
+               (uint64_t)(capacity - 1)};
+  launch_probe<WideLayout, long long, PIPE>(
+      probe, pvalid, nprobe, l, counter, out_build, out_probe, out_capacity,
+      build_matched, fill, idxmap, stream);
+}
+
+// key_i32 != 0: keys are a 4-byte int column read in place, else int64
+void srj_join_build_n32(const void* keys, int32_t key_i32, const uint8_t* valid,
+                        int64_t nrows, void* slots, int64_t capacity,
+                        long long kmin, hipStream_t stream) {
+  int64_t g = grid_1d((nrows + PIPE - 1) / PIPE);
+  auto* sl = reinterpret_cast<unsigned long long*>(slots);
+  uint64_t mask = (uint64_t)(capacity - 1);
+  if (key_i32)
+    join_build_n32_kernel<int><<<g, DEFAULT_BLOCK, 0, stream>>>(
+        reinterpret_cast<const int*>(keys), valid, nrows, sl, mask, kmin);
+  else
+    join_build_n32_kernel<long long><<<g, DEFAULT_BLOCK, 0, stream>>>(
+        reinterpret_cast<const long long*>(keys), valid, nrows, sl, mask, kmin);
+}
+
+void srj_join_probe_n32(const void* probe, int32_t key_i32,
+                        const uint8_t* pvalid, int64_t nprobe, const void* slots,
+                        int64_t capacity, long long kmin, uint64_t* counter,
+                        int32_t* out_build, int64_t* out_probe,
+                        int64_t out_capacity, uint8_t* build_matched,
+                        int32_t fill, const int32_t* idxmap,
+                        hipStream_t stream) {
+  NarrowLayout l{reinterpret_cast<const unsigned long long*>(slots),
+                 (uint64_t)(capacity - 1), kmin};
+  if (key_i32)
+    launch_probe<NarrowLayout, int, PIPE>(
+        reinterpret_cast<const int*>(probe), pvalid, nprobe, l, counter,
+        out_build, out_probe, out_capacity, build_matched, fill, idxmap,
+        stream);
+  else
+    launch_probe<NarrowLayout, long long, PIPE>(
+        reinterpret_cast<const long long*>(probe), pvalid, nprobe, l, counter,
+        out_build, out_probe, out_capacity, build_matched, fill, idxmap,
+        stream);
+}
+
+// slots: `range` zeroed words; flag: one zeroed word (see the kernel).
+void srj_join_build_d32(const void* keys, int32_t key_i32,
+                        const uint8_t* valid, int64_t nrows, void* slots,
+                        int64_t range, long long kmin, uint32_t* flag,
+                        hipStream_t stream) {
+  int64_t g = grid_1d((nrows + DPIPE - 1) / DPIPE);
+  auto* sl = reinterpret_cast<uint32_t*>(slots);
+  if (key_i32)
+    join_build_d32_kernel<int><<<g, DEFAULT_BLOCK, 0, stream>>>(
+        reinterpret_cast<const int*>(keys), valid, nrows, sl, (uint64_t)range,
+        kmin, flag);
+  else
+    join_build_d32_kernel<long long><<<g, DEFAULT_BLOCK, 0, stream>>>(
+        reinterpret_cast<const long long*>(keys), valid, nrows, sl,
+        (uint64_t)range, kmin, flag);
+}
+
+}  // extern "C"
+
+template <typename K>
+static void probe_d32(const void* probe, const uint8_t* pvalid, int64_t nprobe,
+                      DenseLayout l, uint64_t* counter, int32_t* out_build,
+                      int64_t* out_probe, int64_t out_capacity,
+                      uint8_t* build_matched, int32_t fill,
+                      hipStream_t stream) {
+  auto* p = reinterpret_cast<const K*>(probe);
+  if (l.range <= DENSE_PIPE16_MAX_SLOTS)
+    launch_probe<DenseLayout, K, 16>(p, pvalid, nprobe, l, counter, out_build,
+                                     out_probe, out_capacity, build_matched,
+                                     fill, nullptr, stream);
+  else
+    launch_probe<DenseLayout, K, 8>(p, pvalid, nprobe, l, counter, out_build,
+                                    out_probe, out_capacity, build_matched,
+                                    fill, nullptr, stream);
+}
+
+extern "C" void srj_join_probe_d32(const void* probe, int32_t key_i32,
+                                   const uint8_t* pvalid, int64_t nprobe,
+                                   const void* slots, int64_t range,
+                                   long long kmin, uint64_t* counter,
+                                   int32_t* out_build, int64_t* out_probe,
+                                   int64_t out_capacity, uint8_t* build_matched,
+                                   int32_t fill, hipStream_t stream) {
+  DenseLayout l{reinterpret_cast<const uint32_t*>(slots), (uint64_t)range,
+                kmin};
+  if (key_i32)
+    probe_d32<int>(probe, pvalid, nprobe, l, counter, out_build, out_probe,
+                   out_capacity, build_matched, fill, stream);
+  else
+    probe_d32<long long>(probe, pvalid, nprobe, l, counter, out_build,
+                         out_probe, out_capacity, build_matched, fill, stream);
+}

@@ -4,7 +4,7 @@
 //
 // Reference analog: cudf's hash partition under spark-rapids' shuffle; here
 // it exists to make the NDS join probe LLC-local: the i64 table indexes
-// slots by the TOP hash bits (hashtable_i64.hip slot_of), so keys grouped by
+// slots by the TOP hash bits (i64_slots.hpp slot_of), so keys grouped by
 // the same prefix probe a contiguous ~128 MiB table window that fits the
 // 256 MiB Infinity Cache instead of walking 64 GB at random.
 //
