@@ -372,13 +372,17 @@ class HashJoinTable:
         counter = torch.zeros(1, dtype=torch.int64, device=dev)
         if not fast:
             bdesc, btop, pdesc, ptop, keep = self._descs(pcols)
-        # NOTE measured negative: radix-partitioning the probe keys by hash
-        # prefix (part_hist/part_scatter + idxmap probe) did NOT speed up the
-        # 10B x 1B config — each 64B table line is touched only ~1.4x per 1B
-        # chunk, so LLC locality saves almost no DRAM traffic while the
-        # scatter adds 29 ms/chunk (profiles/r01_bench_join_22.1B.json).
-        # The kernels stay exposed (g.part_hist/part_scatter, idxmap probe)
-        # for schema-partitioned shuffle use; the probe here stays direct.
+        # Measured and rejected, twice: grouping the probe rows by table
+        # window before the probe. By hash prefix into a 64 GiB hashed table
+        # (part_hist/part_scatter + idxmap probe) each 64 B line is touched
+        # only ~1.4x per 1B chunk and the scatter cost 29 ms per chunk
+        # (profiles/r01_bench_join_22.1B.json). By key range into the 3.7 GiB
+        # dense table, with a 5 ms histogram + scatter, the probe over the
+        # grouped rows still took 20 ms per chunk against 25.5 direct: windows
+        # of 32 - 128 MiB hit the Infinity Cache, not the 4 MiB L2s, and random
+        # 64 B lines come from either at the same ~3 TB/s (docs/PERF.md,
+        # "workgroup append"). The probe stays direct; part_hist/part_scatter
+        # and the idxmap probe stay exposed for schema-partitioned shuffle use.
         if out_hint is None:
             if fast:
                 self._probe_fast(p, counter, 0, 0, 0, 0, 0, stream)

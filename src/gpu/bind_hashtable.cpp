@@ -46,9 +46,14 @@ void srj_join_build_d32(const void*, int32_t, const uint8_t*, int64_t, void*,
 void srj_join_probe_d32(const void*, int32_t, const uint8_t*, int64_t,
                         const void*, int64_t, long long, uint64_t*, int32_t*,
                         int64_t*, int64_t, uint8_t*, int32_t, hipStream_t);
+int32_t srj_join_probe_tile(int32_t);
 }
 
 void register_hashtable(py::module_& m) {
+  m.attr("JOIN_PROBE_TILE") =
+      py::dict(py::arg("wide") = srj_join_probe_tile(0),
+               py::arg("narrow") = srj_join_probe_tile(1),
+               py::arg("dense") = srj_join_probe_tile(2));
   m.def("join_build",
         [](uintptr_t cols, uintptr_t top, int32_t ntop, int64_t nrows,
            uintptr_t slots, int64_t capacity, uintptr_t stream) {

@@ -85,7 +85,9 @@ struct WideLayout {
   using Word = longlong2;  // {key, row1} in one load
   using Index = uint64_t;
   static constexpr bool CHAINED = true;
-  static constexpr bool PLAIN_BATCH = false;
+  // per wave and batch: at 2^28 slots of 16 bytes and 4 waves per SIMD the
+  // workgroup append's barriers cost 1.3 % (docs/PERF.md)
+  static constexpr bool WG_APPEND = false;
   const longlong2* slots;
   uint64_t mask;
 
@@ -167,7 +169,7 @@ struct NarrowLayout {
   using Word = unsigned long long;
   using Index = uint64_t;
   static constexpr bool CHAINED = true;
-  static constexpr bool PLAIN_BATCH = false;
+  static constexpr bool WG_APPEND = true;
   const unsigned long long* slots;
   uint64_t mask;
   long long kmin;
@@ -271,7 +273,7 @@ struct DenseLayout {
   using Word = uint32_t;
   using Index = uint32_t;
   static constexpr bool CHAINED = false;
-  static constexpr bool PLAIN_BATCH = true;
+  static constexpr bool WG_APPEND = true;
   const uint32_t* slots;
   uint64_t range;
   long long kmin;
@@ -287,18 +289,23 @@ struct DenseLayout {
   __device__ static uint32_t row1(Word w) { return w; }
 };
 
-// Dense probe rows per lane and batch, chosen by measurement (docs/PERF.md):
-// 16 while the table fits the 256 MiB Infinity Cache (half the wave-wide
-// appends, 1.7x the probe rate at 2^20 and 2^26 slots), 8 beyond it, where
-// the probe lives on waves in flight (29.1 against 31.4 ms per 1B rows into
-// 1B slots).
-constexpr uint64_t DENSE_PIPE16_MAX_SLOTS = 1ull << 26;
+// Dense probe geometry, chosen by measurement (docs/PERF.md): 8 rows per lane
+// keeps 8 waves per SIMD, and a 1024-thread workgroup reserves output space
+// once per 8192 rows. With the workgroup append, 16 rows per lane no longer
+// win at any table size.
+constexpr int DENSE_PPIPE = 8;
+constexpr int DENSE_BLOCK = 1024;
 
 }  // namespace srj
 
 using namespace srj;
 
 extern "C" {
+
+// probe rows per workgroup and iteration: layout 0 wide, 1 narrow, 2 dense
+int32_t srj_join_probe_tile(int32_t layout) {
+  return layout == 2 ? DENSE_BLOCK * DENSE_PPIPE : DEFAULT_BLOCK * PIPE;
+}
 
 void srj_join_build_i64(const long long* keys, const uint8_t* valid, int64_t nrows,
                         void* slots, int64_t capacity, hipStream_t stream) {
@@ -317,7 +324,7 @@ void srj_join_probe_i64(const long long* probe, const uint8_t* pvalid,
                         const int32_t* idxmap, hipStream_t stream) {
   WideLayout l{reinterpret_cast<const longlong2*>(slots),
                (uint64_t)(capacity - 1)};
-  launch_probe<WideLayout, long long, PIPE>(
+  launch_probe<WideLayout, long long, PIPE, DEFAULT_BLOCK>(
       probe, pvalid, nprobe, l, counter, out_build, out_probe, out_capacity,
       build_matched, fill, idxmap, stream);
 }
@@ -347,12 +354,12 @@ void srj_join_probe_n32(const void* probe, int32_t key_i32,
   NarrowLayout l{reinterpret_cast<const unsigned long long*>(slots),
                  (uint64_t)(capacity - 1), kmin};
   if (key_i32)
-    launch_probe<NarrowLayout, int, PIPE>(
+    launch_probe<NarrowLayout, int, PIPE, DEFAULT_BLOCK>(
         reinterpret_cast<const int*>(probe), pvalid, nprobe, l, counter,
         out_build, out_probe, out_capacity, build_matched, fill, idxmap,
         stream);
   else
-    launch_probe<NarrowLayout, long long, PIPE>(
+    launch_probe<NarrowLayout, long long, PIPE, DEFAULT_BLOCK>(
         reinterpret_cast<const long long*>(probe), pvalid, nprobe, l, counter,
         out_build, out_probe, out_capacity, build_matched, fill, idxmap,
         stream);
@@ -375,38 +382,25 @@ void srj_join_build_d32(const void* keys, int32_t key_i32,
         (uint64_t)range, kmin, flag);
 }
 
-}  // extern "C"
-
-template <typename K>
-static void probe_d32(const void* probe, const uint8_t* pvalid, int64_t nprobe,
-                      DenseLayout l, uint64_t* counter, int32_t* out_build,
-                      int64_t* out_probe, int64_t out_capacity,
-                      uint8_t* build_matched, int32_t fill,
-                      hipStream_t stream) {
-  auto* p = reinterpret_cast<const K*>(probe);
-  if (l.range <= DENSE_PIPE16_MAX_SLOTS)
-    launch_probe<DenseLayout, K, 16>(p, pvalid, nprobe, l, counter, out_build,
-                                     out_probe, out_capacity, build_matched,
-                                     fill, nullptr, stream);
-  else
-    launch_probe<DenseLayout, K, 8>(p, pvalid, nprobe, l, counter, out_build,
-                                    out_probe, out_capacity, build_matched,
-                                    fill, nullptr, stream);
-}
-
-extern "C" void srj_join_probe_d32(const void* probe, int32_t key_i32,
-                                   const uint8_t* pvalid, int64_t nprobe,
-                                   const void* slots, int64_t range,
-                                   long long kmin, uint64_t* counter,
-                                   int32_t* out_build, int64_t* out_probe,
-                                   int64_t out_capacity, uint8_t* build_matched,
-                                   int32_t fill, hipStream_t stream) {
+void srj_join_probe_d32(const void* probe, int32_t key_i32,
+                        const uint8_t* pvalid, int64_t nprobe,
+                        const void* slots, int64_t range, long long kmin,
+                        uint64_t* counter, int32_t* out_build,
+                        int64_t* out_probe, int64_t out_capacity,
+                        uint8_t* build_matched, int32_t fill,
+                        hipStream_t stream) {
   DenseLayout l{reinterpret_cast<const uint32_t*>(slots), (uint64_t)range,
                 kmin};
   if (key_i32)
-    probe_d32<int>(probe, pvalid, nprobe, l, counter, out_build, out_probe,
-                   out_capacity, build_matched, fill, stream);
+    launch_probe<DenseLayout, int, DENSE_PPIPE, DENSE_BLOCK>(
+        reinterpret_cast<const int*>(probe), pvalid, nprobe, l, counter,
+        out_build, out_probe, out_capacity, build_matched, fill, nullptr,
+        stream);
   else
-    probe_d32<long long>(probe, pvalid, nprobe, l, counter, out_build,
-                         out_probe, out_capacity, build_matched, fill, stream);
+    launch_probe<DenseLayout, long long, DENSE_PPIPE, DENSE_BLOCK>(
+        reinterpret_cast<const long long*>(probe), pvalid, nprobe, l, counter,
+        out_build, out_probe, out_capacity, build_matched, fill, nullptr,
+        stream);
 }
+
+}  // extern "C"

@@ -1,18 +1,28 @@
 // The join fast path's probe: one software-pipelined kernel over every table
 // layout (join_fast.hip has the layouts and their build kernels).
 //
-// A lane takes PPIPE consecutive probe rows per batch:
-//  * one validity byte per 8 rows gives the batch's live bits, the tail is
-//    clipped, and a key that can never be in the table is masked out;
+// A workgroup takes a tile of BLOCK * PPIPE probe rows per iteration, PPIPE
+// rows per lane:
+//  * chained layouts give a lane PPIPE consecutive rows: one validity byte
+//    per 8 rows gives the batch's live bits and the tail is clipped;
+//    an unchained layout (at most one match per row) interleaves the rows of
+//    a tile instead, row = tile base + b * BLOCK + thread, so that every key
+//    load and every store instruction of a wave covers one contiguous run;
+//  * a key that can never be in the table is masked out;
 //  * keys, then slot indices, then ALL first-slot loads issue back to back
 //    with nothing dependent between them — PPIPE outstanding random loads
 //    per lane are the memory-level parallelism this kernel lives on;
 //  * resolve counts each row's matches and carries the FIRST match's build
 //    row in a register, so the (overwhelmingly common) exactly-one-match row
 //    emits without walking its chain again;
-//  * FILL: one atomicAdd per wave and batch reserves output space (a wave
-//    prefix sum gives each lane its base), then plain stores; only a row
-//    with several matches rescans its chain, cache-warm;
+//  * FILL reserves output space with one atomicAdd per workgroup and tile:
+//    wave totals go through LDS, wave 0 scans them, adds their sum to the
+//    counter and hands every wave its base (two barriers per tile), then
+//    plain stores; only a row with several matches rescans its chain,
+//    cache-warm. The interleaved mapping numbers its pairs b-major, so each
+//    store instruction writes one contiguous run of out_build and out_probe.
+//    A layout with WG_APPEND = false reserves per wave and batch instead, with
+//    no barrier;
 //  * count mode adds one wave sum per kernel to the counter instead.
 //
 // Contract, for every layout:
@@ -35,59 +45,85 @@
 //           on the rare chain path, so that indices do not stay in registers
 //   empty(Word), match(Word, Tag), chain(Word), row1(Word)
 //   CHAINED       false: at most one match per key, no chain walk, no idxmap,
-//                 and next, reindex and chain are not needed
-//   PLAIN_BATCH   true: a batch wholly in range loads its keys unclamped, as
-//                 consecutive loads the compiler merges into wide ones;
-//                 false: every key load is clamped and unconditional
+//                 interleaved rows, and next, reindex and chain are not needed
+//   WG_APPEND     one reservation per workgroup and tile (see above)
 #pragma once
 #include "srj_common.hpp"
 
 namespace srj {
 
-template <typename L, typename K, bool FILL, bool HAS_VALID, int PPIPE>
-__global__ void join_probe_kernel_t(
-    const K* __restrict__ probe, const uint8_t* __restrict__ pvalid,
-    int64_t nprobe, L layout, uint64_t* __restrict__ counter,
-    int32_t* __restrict__ out_build, int64_t* __restrict__ out_probe,
-    int64_t out_capacity, uint8_t* __restrict__ build_matched,
-    const int32_t* __restrict__ idxmap) {
+template <typename L, typename K, bool FILL, bool HAS_VALID, int PPIPE,
+          int BLOCK>
+__global__ void __launch_bounds__(BLOCK, (PPIPE == 8 && !L::CHAINED) ? 8 : 1)
+join_probe_kernel_t(const K* __restrict__ probe,
+                    const uint8_t* __restrict__ pvalid, int64_t nprobe,
+                    L layout, uint64_t* __restrict__ counter,
+                    int32_t* __restrict__ out_build,
+                    int64_t* __restrict__ out_probe, int64_t out_capacity,
+                    uint8_t* __restrict__ build_matched,
+                    const int32_t* __restrict__ idxmap) {
   static_assert(PPIPE == 8 || PPIPE == 16, "validity bytes per batch");
+  static_assert(L::WG_APPEND || L::CHAINED, "b-major needs the LDS table");
   using Tag = typename L::Tag;
   using Word = typename L::Word;
-  int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  int64_t nthreads = (int64_t)gridDim.x * blockDim.x;
-  int lane = threadIdx.x & (WAVE - 1);
+  constexpr bool ROWMAJOR = !L::CHAINED;
+  constexpr int NW = BLOCK / WAVE;
+  // reservation entries of a tile, in output order
+  constexpr int NE = ROWMAJOR ? NW * PPIPE : NW;
+  constexpr int EPL = (NE + WAVE - 1) / WAVE;  // entries per lane of wave 0
+  constexpr int64_t TILE = (int64_t)BLOCK * PPIPE;
+  constexpr int64_t STEP = ROWMAJOR ? BLOCK : 1;  // row = base + b * STEP
+  __shared__ uint32_t cnt[NE];
+  __shared__ uint64_t offs[NE];
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int wave = threadIdx.x / WAVE;
   uint64_t count_local = 0;
-  int64_t nbatch = (nprobe + (int64_t)PPIPE - 1) / PPIPE;
-  // pad so every lane of a wave runs the same iterations (wave shuffles)
-  int64_t nbatch_pad = (nbatch + WAVE - 1) & ~(int64_t)(WAVE - 1);
-  for (int64_t batch = tid; batch < nbatch_pad; batch += nthreads) {
-    bool batch_ok = batch < nbatch;
-    int64_t base = batch_ok ? batch * PPIPE : 0;
+  const int64_t ntiles = (nprobe + TILE - 1) / TILE;
+  // uniform per workgroup: every thread passes the same barriers
+  for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const int64_t tbase = tile * TILE;
+    const int64_t base = tbase + (int64_t)threadIdx.x * (ROWMAJOR ? 1 : PPIPE);
     uint32_t vbits = (1u << PPIPE) - 1u;
-    if (HAS_VALID) {
-      vbits = pvalid[base >> 3];
-      // the second byte of a 16-row batch may lie past the mask's last byte
-      if (PPIPE == 16 && base + 8 < nprobe)
-        vbits |= (uint32_t)pvalid[(base >> 3) + 1] << 8;
-    }
-    if (base + PPIPE > nprobe) {
-      int64_t tail = nprobe - base;
-      vbits &= (uint32_t)((1u << (tail < 0 ? 0 : tail)) - 1u);
-    }
-    if (!batch_ok) vbits = 0;
     K k[PPIPE];
-    if (L::PLAIN_BATCH && base + PPIPE <= nprobe) {
+    if (ROWMAJOR) {
+      uint32_t vb[PPIPE];
+      if (tbase + TILE <= nprobe) {
+        // a whole tile: one uniform base per b, the thread is the offset
 #pragma unroll
-      for (int b = 0; b < PPIPE; ++b) k[b] = probe[base + b];
+        for (int b = 0; b < PPIPE; ++b) {
+          k[b] = (probe + tbase + b * STEP)[threadIdx.x];
+          vb[b] = HAS_VALID ? (uint32_t)(pvalid + ((tbase + b * STEP) >> 3))
+                                      [threadIdx.x >> 3] >> (threadIdx.x & 7)
+                            : 1u;
+        }
+      } else {
+#pragma unroll
+        for (int b = 0; b < PPIPE; ++b) {
+          int64_t row = base + b * STEP;
+          int64_t crow = row < nprobe ? row : 0;  // clamped, unconditional
+          k[b] = probe[crow];
+          vb[b] = HAS_VALID ? (uint32_t)pvalid[crow >> 3] >> (crow & 7) : 1u;
+          if (row >= nprobe) vb[b] = 0;
+        }
+      }
+      vbits = 0;
+#pragma unroll
+      for (int b = 0; b < PPIPE; ++b) vbits |= (vb[b] & 1u) << b;
     } else {
+      if (HAS_VALID && base < nprobe) {
+        vbits = pvalid[base >> 3];
+        // the second byte of a 16-row batch may lie past the mask's last byte
+        if (PPIPE == 16 && base + 8 < nprobe)
+          vbits |= (uint32_t)pvalid[(base >> 3) + 1] << 8;
+      }
+      if (base + PPIPE > nprobe) {
+        int64_t tail = nprobe - base;
+        vbits &= (uint32_t)((1u << (tail < 0 ? 0 : tail)) - 1u);
+      }
 #pragma unroll
       for (int b = 0; b < PPIPE; ++b) {
         int64_t row = base + b;
-        if (L::PLAIN_BATCH)
-          k[b] = row < nprobe ? probe[row] : (K)0;  // masked by vbits
-        else
-          k[b] = probe[row < nprobe ? row : 0];  // clamped, unconditional
+        k[b] = probe[row < nprobe ? row : 0];  // clamped, unconditional
       }
     }
     Tag tag[PPIPE];
@@ -139,19 +175,72 @@ __global__ void join_probe_kernel_t(
       count_local += nm;
       continue;
     }
-    uint32_t incl = wave_prefix_incl(nm);
-    uint32_t total = __shfl(incl, WAVE - 1, WAVE);
-    uint64_t wave_base = 0;
-    if (lane == WAVE - 1 && total)
-      wave_base = atomicAdd((unsigned long long*)counter,
-                            (unsigned long long)total);
-    wave_base = __shfl(wave_base, WAVE - 1, WAVE);
-    int64_t pos = (int64_t)(wave_base + incl - nm);
+    // ROWMAJOR: per b, the hits of this wave's lower lanes, a byte each (the
+    // ballots themselves must not stay in scalar registers over the barriers)
+    uint32_t below[ROWMAJOR ? PPIPE / 4 : 1] = {};
+    uint32_t incl = 0;      // lane-major: inclusive wave scan of nm
+    uint64_t wave_base = 0;  // lane-major: first output position of the wave
+    if constexpr (ROWMAJOR) {
+      uint32_t mine = 0;
+#pragma unroll
+      for (int b = 0; b < PPIPE; ++b) {
+        uint64_t m = __ballot((hit >> b) & 1);
+        below[b / 4] |= __builtin_amdgcn_mbcnt_hi(
+                            (uint32_t)(m >> 32),
+                            __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u))
+                        << (8 * (b % 4));
+        if (lane == b) mine = (uint32_t)__popcll(m);
+      }
+      // one entry per (b, wave), b-major
+      if (lane < PPIPE) cnt[lane * NW + wave] = mine;
+    } else {
+      incl = wave_prefix_incl(nm);
+      if (L::WG_APPEND && lane == WAVE - 1) cnt[wave] = incl;
+    }
+    if constexpr (L::WG_APPEND) {
+      __syncthreads();
+      if (wave == 0) {
+        uint32_t c[EPL], sum = 0;
+#pragma unroll
+        for (int e = 0; e < EPL; ++e) {
+          int i = lane * EPL + e;
+          c[e] = i < NE ? cnt[i] : 0u;
+          sum += c[e];
+        }
+        uint32_t sincl = wave_prefix_incl(sum);
+        uint32_t total = __shfl(sincl, WAVE - 1, WAVE);
+        uint64_t run = 0;
+        if (lane == WAVE - 1 && total)
+          run = atomicAdd((unsigned long long*)counter,
+                          (unsigned long long)total);
+        run = __shfl(run, WAVE - 1, WAVE) + sincl - sum;
+#pragma unroll
+        for (int e = 0; e < EPL; ++e) {
+          int i = lane * EPL + e;
+          if (i < NE) offs[i] = run;
+          run += c[e];
+        }
+      }
+      // offs is rewritten only behind the next tile's first barrier, cnt only
+      // behind this one: two barriers per tile are enough
+      __syncthreads();
+      if (!ROWMAJOR) wave_base = offs[wave];
+    } else {
+      uint32_t total = __shfl(incl, WAVE - 1, WAVE);
+      if (lane == WAVE - 1 && total)
+        wave_base = atomicAdd((unsigned long long*)counter,
+                              (unsigned long long)total);
+      wave_base = __shfl(wave_base, WAVE - 1, WAVE);
+    }
     if (hit) {
+      int64_t pos = (int64_t)(wave_base + incl - nm);
 #pragma unroll
       for (int b = 0; b < PPIPE; ++b) {
         if (!((hit >> b) & 1)) continue;
-        int64_t prow = base + b;
+        int64_t prow = base + b * STEP;
+        if constexpr (ROWMAJOR)
+          pos = (int64_t)offs[b * NW + wave] +
+                ((below[b / 4] >> (8 * (b % 4))) & 0xffu);
         auto emit = [&](uint32_t r1) {
           if (pos < out_capacity) {
             out_build[pos] = (int32_t)(r1 - 1);
@@ -190,17 +279,17 @@ __global__ void join_probe_kernel_t(
 }
 
 // The one fill x validity ladder. Count mode passes null outputs.
-template <typename L, typename K, int PPIPE>
+template <typename L, typename K, int PPIPE, int BLOCK>
 void launch_probe(const K* probe, const uint8_t* pvalid, int64_t nprobe,
                   L layout, uint64_t* counter, int32_t* out_build,
                   int64_t* out_probe, int64_t out_capacity,
                   uint8_t* build_matched, int32_t fill, const int32_t* idxmap,
                   hipStream_t stream) {
   auto kernel =
-      fill ? (pvalid ? join_probe_kernel_t<L, K, true, true, PPIPE>
-                     : join_probe_kernel_t<L, K, true, false, PPIPE>)
-           : (pvalid ? join_probe_kernel_t<L, K, false, true, PPIPE>
-                     : join_probe_kernel_t<L, K, false, false, PPIPE>);
+      fill ? (pvalid ? join_probe_kernel_t<L, K, true, true, PPIPE, BLOCK>
+                     : join_probe_kernel_t<L, K, true, false, PPIPE, BLOCK>)
+           : (pvalid ? join_probe_kernel_t<L, K, false, true, PPIPE, BLOCK>
+                     : join_probe_kernel_t<L, K, false, false, PPIPE, BLOCK>);
   if (!fill) {
     out_build = nullptr;
     out_probe = nullptr;
@@ -208,9 +297,13 @@ void launch_probe(const K* probe, const uint8_t* pvalid, int64_t nprobe,
     build_matched = nullptr;
     idxmap = nullptr;
   }
-  kernel<<<grid_1d((nprobe + PPIPE - 1) / PPIPE), DEFAULT_BLOCK, 0, stream>>>(
-      probe, pvalid, nprobe, layout, counter, out_build, out_probe,
-      out_capacity, build_matched, idxmap);
+  // one tile of BLOCK * PPIPE rows per workgroup and iteration; the cap
+  // keeps MAX_GRID * DEFAULT_BLOCK threads whatever the workgroup size
+  kernel<<<grid_1d((nprobe + PPIPE - 1) / PPIPE, BLOCK,
+                   MAX_GRID * DEFAULT_BLOCK / BLOCK),
+           BLOCK, 0, stream>>>(probe, pvalid, nprobe, layout, counter,
+                               out_build, out_probe, out_capacity,
+                               build_matched, idxmap);
 }
 
 }  // namespace srj
