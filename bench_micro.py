@@ -469,6 +469,73 @@ def join_dense_bench(nb, npr, iters, dev, g):
         tables.clear()
 
 
+def join_modes_bench(nb, npr, iters, dev, g):
+    """Semi, anti and left outer joins as emit modes of the fast-path probe
+    (semi_select, left_outer_join) against the parent's expressions, copied
+    here: HashJoinTable.semi_join, and inner_join plus make_left_outer. Forced
+    wide, narrow and dense tables over the same duplicate-free int64 keys;
+    probe keys uniform over nb / rate values, so `rate` of them match. The two
+    paths alternate; results are compared before timing. The parent's semi
+    join is timed as NDS pays it, on a table that was built for this join
+    alone: its generic second table is dropped before every call."""
+    from spark_rapids_jni_amd.columnar import Column, DType
+    from spark_rapids_jni_amd.ops.join import HashJoinTable, make_left_outer
+    bcol = Column(DType.INT64, nb, torch.randperm(nb, dtype=torch.int64,
+                                                  device=dev, generator=g))
+    kw = {"wide": {"narrow": False}, "narrow": {"narrow": True},
+          "dense": {"dense": True}}
+
+    def pair_key(bi, pi):
+        return torch.sort(pi * (nb + 1) + (bi.long() + 1))[0]
+
+    for rate in (0.1, 0.5, 1.0):
+        pcol = Column(DType.INT64, npr, torch.randint(
+            0, int(nb / rate), (npr,), dtype=torch.int64, device=dev,
+            generator=g))
+        for layout in kw:
+            tbl = HashJoinTable.build(bcol, **kw[layout])
+            assert tbl.layout == layout
+
+            def parent_semi(anti):
+                def run():
+                    if hasattr(tbl, "_generic"):
+                        del tbl._generic
+                    return tbl.semi_join(pcol, anti=anti)
+                return run
+
+            def parent_left():
+                bi, pi = tbl.inner_join(pcol)
+                return make_left_outer(npr, bi, pi)
+
+            cells = {
+                "semi": (lambda: tbl.semi_select(pcol), parent_semi(False)),
+                "anti": (lambda: tbl.semi_select(pcol, anti=True),
+                         parent_semi(True)),
+                "left": (lambda: tbl.left_outer_join(pcol), parent_left),
+            }
+            for kind, (new_fn, old_fn) in cells.items():
+                a, b = new_fn(), old_fn()
+                if kind == "left":
+                    assert torch.equal(pair_key(*a), pair_key(*b))
+                    out_rows = a[0].numel()
+                else:
+                    assert torch.equal(a, torch.sort(b)[0])
+                    out_rows = a.numel()
+                del a, b
+                new_s, old_s = ab_time(new_fn, old_fn, iters, repeats=3)
+                for path, xs in (("native", new_s), ("parent", old_s)):
+                    xs = sorted(xs)
+                    print(json.dumps({
+                        "bench": "join_modes", "layout": layout, "kind": kind,
+                        "match_rate": rate, "path": path, "build_rows": nb,
+                        "probe_rows": npr, "out_rows": out_rows,
+                        "ms": round(xs[1] * 1e3, 4),
+                        "ms_min": round(xs[0] * 1e3, 4),
+                        "ms_max": round(xs[2] * 1e3, 4),
+                        "rows_per_sec": round(npr / xs[1], 1)}), flush=True)
+            tbl = None
+
+
 def plumbing_bench():
     """BASELINE config[0]: murmur3 + row<->columnar on a 1k-row int64 batch
     via the HOST path (no GPU) — measures binding/plumbing overhead like the
@@ -500,8 +567,8 @@ def main():
     ap.add_argument("--rows", type=int, default=2**24)
     ap.add_argument("--iters", type=int, default=5)
     ap.add_argument("--only", choices=["sort_order", "join_narrow",
-                                      "join_dense", "window", "expr",
-                                      "groupby_sorted"],
+                                      "join_dense", "join_modes", "window",
+                                      "expr", "groupby_sorted"],
                     default=None,
                     help="run just this group")
     args = ap.parse_args()
@@ -542,6 +609,13 @@ def main():
         # beyond the Infinity Cache, then cache resident
         for nb, npr in ((2**26, 2**26), (2**20, 2**24)):
             join_dense_bench(nb, npr, args.iters, "cuda", g)
+        return
+    if args.only == "join_modes":
+        g = torch.Generator(device="cuda")
+        g.manual_seed(7)
+        # cache resident, then beyond the Infinity Cache
+        for nb, npr in ((2**20, 2**24), (2**26, 2**26)):
+            join_modes_bench(nb, npr, args.iters, "cuda", g)
         return
     plumbing_bench()  # CPU shape (BASELINE config[0]) first
     n = args.rows

@@ -120,14 +120,40 @@ class Frame:
             from ..ops.compact import gather_tensors
             return self._rebuild(
                 gather_tensors(self._tensors(), idx.long()), idx.numel())
-        # outer join: a negative entry makes a null row
+        # outer join: a negative entry makes a null row. gather_tensors
+        # writes zero for an entry outside [0, nrows): one fused call moves
+        # every data and validity tensor, a gathered validity is false under
+        # a negative entry already, and columns without one share idx >= 0.
+        # The data word under a null row is 0.
+        from ..ops.compact import gather_tensors
+        n = idx.numel()
+        idx = idx.long()
+        if self.nrows == 0 or not idx.is_cuda:
+            # empty side of an outer join: all rows are null; CPU tensors
+            # (the oracle) cannot index with -1
+            return self._gather_null_for_neg_torch(idx)
+        ts = gather_tensors(self._tensors(), idx)
+        it = iter(ts)
+        nonneg = None
+        out = {}
+        for name, v in self.cols.items():
+            data = next(it)
+            if v.valid is not None:
+                valid = next(it)
+            else:
+                if nonneg is None:
+                    nonneg = idx >= 0
+                valid = nonneg
+            out[name] = Val(data, valid, v.dict)
+        return Frame(out, n, self.sharded)
+
+    def _gather_null_for_neg_torch(self, idx: torch.Tensor) -> "Frame":
         out = {}
         n = idx.numel()
         neg = idx < 0
         safe = idx.clamp(min=0)
         for name, v in self.cols.items():
             if v.data.numel() == 0:
-                # empty side of an outer join: all rows are null
                 data = torch.zeros(n, dtype=v.data.dtype,
                                    device=idx.device)
                 out[name] = Val(data, torch.zeros(
@@ -312,25 +338,36 @@ class GpuBackend:
                 from ..ops.compact import nonzero
                 sel = nonzero(matched if how == "semi" else ~matched)
                 return sel, None
+            # probes the table just built; ascending under ordered_joins too
             tbl = HashJoinTable.build(bcols)
-            sel = tbl.semi_join(pcols, anti=(how == "anti"))
-            if self.ordered_joins:
-                sel = torch.sort(sel)[0]
-            return sel, None
+            return tbl.semi_select(pcols, anti=(how == "anti")), None
         tbl = HashJoinTable.build(bcols)
         if how == "full":
-            from ..ops.join import make_full_outer, make_left_outer
-            bi, pi, matched = tbl.inner_join(pcols, track_build_matches=True)
-            bi, pi = self._ordered_pairs(bi, pi, nleft)
-            fb, fp = make_full_outer(matched, bi, pi, nleft)
+            from ..ops.join import append_unmatched_build
+            lb, lp, matched = tbl.left_outer_join(pcols,
+                                                  track_build_matches=True)
+            lb, lp = self._ordered_outer_pairs(lb, lp, nleft)
+            fb, fp = append_unmatched_build(matched, lb, lp)
             return fp, fb  # -1 entries on both sides
+        if how == "left":
+            lb, lp = tbl.left_outer_join(pcols)
+            lb, lp = self._ordered_outer_pairs(lb, lp, nleft)
+            return lp, lb.long()  # (left_idx, right_idx with -1 for unmatched)
         bi, pi = tbl.inner_join(pcols)
         bi, pi = self._ordered_pairs(bi, pi, nleft)
-        if how == "left":
-            from ..ops.join import make_left_outer
-            lb, lp = make_left_outer(nleft, bi, pi)
-            return lp, lb  # (left_idx, right_idx with -1 for unmatched)
         return pi, bi.long()
+
+    def _ordered_outer_pairs(self, lb, lp, nleft: int):
+        """The pairs of a left outer join in the order `_ordered_pairs` plus
+        `make_left_outer` give: matches by (left row, right row), then the
+        unmatched left rows ascending. One sort, "is unmatched" leading."""
+        if not self.ordered_joins or lp.numel() < 2:
+            return lb, lp
+        from ..ops.sort import sort_order_tensors
+        order = sort_order_tensors(
+            [lb < 0, lp, lb],
+            key_bits=[None, max(1, (max(nleft, 1) - 1).bit_length()), None])
+        return lb[order], lp[order]
 
     def _ordered_pairs(self, bi, pi, nleft: int):
         """The matches of an inner join sorted by (left row, right row)."""

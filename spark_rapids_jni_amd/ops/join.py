@@ -8,6 +8,15 @@ hash_inner_join producing gather maps, plus gather-map algebra
 MI355X design: a multimap of packed (fingerprint32|row+1) u64 slots at 50%
 load, linear probing (src/gpu/hashtable.hip). Build side is capped at 2^31-1
 rows (the reference has the same per-column row cap); probe side is int64.
+
+Which to prefer. Semi, anti, left and full outer joins are first-class probes
+of a HashJoinTable: `semi_select` / `probe_matches`, `left_outer_join` and
+`full_outer_join`. On the fast-path tables they are emit modes of the one
+probe kernel (src/gpu/join_probe.hpp); on the generic table they fall back to
+the compositions below. `semi_join` and the gather-map algebra
+`make_left_outer` / `make_full_outer` over `inner_join` remain, unchanged,
+for callers that hold an inner-join result already or need the generic
+kernels.
 """
 from typing import List, Optional, Sequence, Tuple, Union
 
@@ -67,6 +76,9 @@ _I32_KMIN = -(1 << 31)
 # a key range of at most this many slots per build row takes the direct-
 # address table: at most 8 B per build row, a quarter of the narrow table
 DENSE_MAX_SLOTS_PER_ROW = 2
+# `mode` of the join_probe_mode_* entry points: ProbeEmit in join_probe.hpp
+# (its INNER = 0 is what join_probe_i64 / _n32 / _d32 run)
+PROBE_OUTER, PROBE_FLAG = 1, 2
 
 
 def _is_dense(lo: int, hi: int, n: int) -> bool:
@@ -129,11 +141,13 @@ def _pack_ranges(cols: List[Column]):
     return mins, widths
 
 
-def _pack_keys(cols: List[Column], mins, widths):
+def _pack_keys(cols: List[Column], mins, widths, drop_all_valid=True):
     """Fold key columns into (packed int64, validity bitmask|None) using the
     given ranges. Rows with a null key or an out-of-range value (probe side
     of a join: can never match) get their validity bit cleared — join
-    semantics, where nulls never match."""
+    semantics, where nulls never match. An all-valid mask is dropped, which
+    costs one read-back; drop_all_valid=False keeps the mask whatever it
+    holds and reads nothing back."""
     from ..columnar import validity_to_bool
     n = cols[0].size
     dev = cols[0].device
@@ -146,7 +160,7 @@ def _pack_keys(cols: List[Column], mins, widths):
             in_range &= validity_to_bool(c.validity, n)
         ok &= in_range
         packed = packed * w + torch.where(in_range, v, torch.zeros_like(v))
-    if bool(ok.all().item()):
+    if drop_all_valid and bool(ok.all().item()):
         return packed, None
     from ..ops.aggregate import _validity_from_bool
     return packed, _validity_from_bool(ok)
@@ -169,6 +183,14 @@ class HashJoinTable:
     its one probe kernel, src/gpu/join_probe.hpp. `capacity` is the slot
     count in every layout; it is a power of two except for dense, where it is
     the key range.
+
+    Probes: `inner_join`, `left_outer_join`, `full_outer_join` give gather
+    maps; `semi_select` gives the ascending probe rows of a semi or anti
+    join, `probe_matches` their per-probe-row flags and `mark_matches` the
+    per-build-row ones. All of them run on every layout and probe the table
+    that was built. `semi_join` is the older form of `semi_select`: on a
+    fast-path table it builds and probes a second, generic table and its row
+    order is unspecified; prefer `semi_select`.
     """
 
     def __init__(self, build_keys: List[Column], slots: torch.Tensor,
@@ -318,16 +340,19 @@ class HashJoinTable:
         pdesc, ptop, pkeep = pack_descriptors(probe_cols)
         return bdesc, btop, pdesc, ptop, (bkeep, pkeep, bdesc, btop, pdesc, ptop)
 
-    def _fast_probe_col(self, pcols: List[Column]) -> Optional[Column]:
+    def _fast_probe_col(self, pcols: List[Column],
+                        sync: bool = True) -> Optional[Column]:
         """The single key column the fast-path probe kernels read, or None
-        when this probe has to take the generic kernels."""
+        when this probe has to take the generic kernels. `sync=False` packs
+        a multi-key probe without the read-back that drops an all-valid
+        mask (see _pack_keys)."""
         pack = getattr(self, "_pack", None)
         if not self.i64_fast:
             return None
         if pack is not None:
             if len(pcols) != len(self.build_keys):
                 return None
-            packed, pvalid = _pack_keys(pcols, *pack)
+            packed, pvalid = _pack_keys(pcols, *pack, drop_all_valid=sync)
             return Column(pcols[0].dtype, pcols[0].size, packed, pvalid,
                           null_count=None)
         if not _is_i64_fast(pcols):
@@ -358,6 +383,133 @@ class HashJoinTable:
                              counter.data_ptr(), out_build, out_probe,
                              out_capacity, matched, fill, 0, stream)
 
+    def _probe_mode(self, p: Column, mode: int, counter, out_build, out_probe,
+                    out_capacity, matched, fill, probe_hit, anti, stream):
+        """One probe in an emit mode of join_probe.hpp (PROBE_*)."""
+        g = _native.gpu()
+        pvalid = p.validity.data_ptr() if p.validity is not None else 0
+        if self.layout == "wide":
+            g.join_probe_mode_i64(p.data.data_ptr(), pvalid, p.size,
+                                  self.slots.data_ptr(), self.capacity,
+                                  counter, out_build, out_probe, out_capacity,
+                                  matched, fill, mode, probe_hit, anti, stream)
+            return
+        data, key_i32 = _narrow_keys(p)
+        fn = (g.join_probe_mode_d32 if self.layout == "dense"
+              else g.join_probe_mode_n32)
+        fn(data.data_ptr(), key_i32, pvalid, p.size, self.slots.data_ptr(),
+           self.capacity, self.kmin, counter, out_build, out_probe,
+           out_capacity, matched, fill, mode, probe_hit, anti, stream)
+
+    def probe_matches(self, probe, anti: bool = False) -> torch.Tensor:
+        """Per-PROBE-row flags (uint8): 1 where the row has a match, or, with
+        `anti`, where it has none. The mirror of `mark_matches`. A null key
+        never matches, so `anti` flags it. No pair is materialized and nothing
+        is counted: on the fast-path tables this is one pass of the probe
+        kernel in its flag mode, with no atomic and no read-back. The result
+        is the [:nprobe] view of a buffer padded to 16 bytes."""
+        pcols = _keys(probe)
+        # a packed probe keeps its validity mask unchecked: no read-back
+        p = self._fast_probe_col(pcols, sync=False)
+        if p is None:
+            flags = torch.zeros(pcols[0].size, dtype=torch.uint8,
+                                device=pcols[0].device)
+            flags[self.semi_join(pcols, anti)] = 1
+            return flags
+        return self._probe_flags(p, anti)
+
+    def _probe_flags(self, p: Column, anti: bool) -> torch.Tensor:
+        """`probe_matches` over an already resolved fast-path key column."""
+        nprobe = p.size
+        buf = torch.empty((nprobe + 15) // 16 * 16, dtype=torch.uint8,
+                          device=p.data.device)
+        if nprobe:
+            self._probe_mode(p, PROBE_FLAG, 0, 0, 0, 0, 0,
+                             0, buf.data_ptr(), 1 if anti else 0,
+                             _native.current_stream())
+        return buf[:nprobe]
+
+    def semi_select(self, probe, anti: bool = False) -> torch.Tensor:
+        """Left semi/anti join: the probe rows with a match (without one for
+        `anti`), int64, in ASCENDING order: the flags of `probe_matches` and
+        one stable compaction, whose kept-row count is the one read-back, on
+        packed multi-key tables too. Prefer this to `semi_join`, which builds
+        a second, generic table over a fast-path table's keys and returns the
+        rows in no fixed order."""
+        from .compact import nonzero
+        pcols = _keys(probe)
+        p = self._fast_probe_col(pcols, sync=False)
+        if p is None:
+            return torch.sort(self.semi_join(pcols, anti))[0]
+        return nonzero(self._probe_flags(p, anti))
+
+    def left_outer_join(self, probe, out_hint: Optional[int] = None,
+                        track_build_matches: bool = False):
+        """LEFT OUTER join with the probe side as left. Returns (build_idx
+        int32, probe_idx int64[, build_matched uint8]): every matching pair,
+        and one pair with build index -1 for every probe row without a match
+        (null keys included). Count, `out_hint` and the rerun on a hint that
+        is too small work as in `inner_join`; the size is matching pairs plus
+        unmatched probe rows. Pair order is unspecified. On the fast-path
+        tables the probe kernel emits the -1 pairs itself; prefer this to
+        `make_left_outer(inner_join(...))`."""
+        pcols = _keys(probe)
+        nprobe = pcols[0].size
+        dev = pcols[0].device
+        p = self._fast_probe_col(pcols)
+        if p is None:
+            res = self.inner_join(pcols, out_hint, track_build_matches)
+            lb, lp = make_left_outer(nprobe, res[0], res[1])
+            return (lb.to(torch.int32), lp) + tuple(res[2:])
+        stream = _native.current_stream()
+
+        def launch(counter, out_build, out_probe, capacity, matched, fill):
+            self._probe_mode(p, PROBE_OUTER, counter.data_ptr(), out_build,
+                             out_probe, capacity, matched, fill, 0, 0, stream)
+        return self._gather_maps(launch, dev, out_hint, track_build_matches)
+
+    def _gather_maps(self, launch, dev, out_hint: Optional[int],
+                     track_build_matches: bool):
+        """The count / hint / rerun protocol of every probe that returns
+        gather maps. `launch(counter, out_build, out_probe, capacity,
+        matched, fill)` runs one probe: fill = 0 counts only (null outputs),
+        fill = 1 writes up to `capacity` pairs and counts them all. Without
+        a hint a count pass sizes the outputs; a hint that proves too small
+        costs a second fill pass with the exact size."""
+        counter = torch.zeros(1, dtype=torch.int64, device=dev)
+        if out_hint is None:
+            launch(counter, 0, 0, 0, 0, 0)
+            total = int(counter.item())
+            counter.zero_()
+        else:
+            total = out_hint
+        out_build = torch.empty(max(total, 1), dtype=torch.int32, device=dev)
+        out_probe = torch.empty(max(total, 1), dtype=torch.int64, device=dev)
+        matched = (torch.zeros(self.num_build_rows, dtype=torch.uint8,
+                               device=dev)
+                   if track_build_matches else None)
+        launch(counter, out_build.data_ptr(), out_probe.data_ptr(), total,
+               matched.data_ptr() if matched is not None else 0, 1)
+        actual = int(counter.item())
+        if actual > total:
+            # hint was too small: rerun with the exact size
+            return self._gather_maps(launch, dev, actual,
+                                     track_build_matches)
+        out_build = out_build[:actual]
+        out_probe = out_probe[:actual]
+        if track_build_matches:
+            return out_build, out_probe, matched
+        return out_build, out_probe
+
+    def full_outer_join(self, probe, out_hint: Optional[int] = None):
+        """FULL OUTER join. Returns (build_idx int64, probe_idx int64) with
+        -1 on either side: the `left_outer_join` pairs (`out_hint` is theirs),
+        then the build rows nothing matched, ascending, with probe index
+        -1."""
+        lb, lp, matched = self.left_outer_join(probe, out_hint,
+                                               track_build_matches=True)
+        return append_unmatched_build(matched, lb, lp)
+
     def inner_join(self, probe: Union[Column, Table, Sequence[Column]],
                    out_hint: Optional[int] = None,
                    track_build_matches: bool = False):
@@ -369,7 +521,6 @@ class HashJoinTable:
         dev = pcols[0].device
         p = self._fast_probe_col(pcols)
         fast = p is not None
-        counter = torch.zeros(1, dtype=torch.int64, device=dev)
         if not fast:
             bdesc, btop, pdesc, ptop, keep = self._descs(pcols)
         # Measured and rejected, twice: grouping the probe rows by table
@@ -383,43 +534,21 @@ class HashJoinTable:
         # 64 B lines come from either at the same ~3 TB/s (docs/PERF.md,
         # "workgroup append"). The probe stays direct; part_hist/part_scatter
         # and the idxmap probe stay exposed for schema-partitioned shuffle use.
-        if out_hint is None:
+        def launch(counter, out_build, out_probe, capacity, matched, fill):
             if fast:
-                self._probe_fast(p, counter, 0, 0, 0, 0, 0, stream)
-            else:
+                self._probe_fast(p, counter, out_build, out_probe, capacity,
+                                 matched, fill, stream)
+            elif not fill:
                 g.join_probe_count(bdesc.data_ptr(), btop.data_ptr(), pdesc.data_ptr(),
                                    ptop.data_ptr(), len(pcols), nprobe,
                                    self.slots.data_ptr(), self.capacity,
                                    counter.data_ptr(), stream)
-            total = int(counter.item())
-            counter.zero_()
-        else:
-            total = out_hint
-        out_build = torch.empty(max(total, 1), dtype=torch.int32, device=dev)
-        out_probe = torch.empty(max(total, 1), dtype=torch.int64, device=dev)
-        matched = (torch.zeros(self.num_build_rows, dtype=torch.uint8, device=dev)
-                   if track_build_matches else None)
-        if fast:
-            self._probe_fast(p, counter, out_build.data_ptr(),
-                             out_probe.data_ptr(), total,
-                             matched.data_ptr() if matched is not None else 0,
-                             1, stream)
-        else:
-            g.join_probe_fill(bdesc.data_ptr(), btop.data_ptr(), pdesc.data_ptr(),
-                              ptop.data_ptr(), len(pcols), nprobe,
-                              self.slots.data_ptr(), self.capacity, counter.data_ptr(),
-                              out_build.data_ptr(), out_probe.data_ptr(), total,
-                              matched.data_ptr() if matched is not None else 0, stream)
-        actual = int(counter.item())
-        if actual > total:
-            # hint was too small: rerun with the exact size
-            return self.inner_join(probe, out_hint=actual,
-                                   track_build_matches=track_build_matches)
-        out_build = out_build[:actual]
-        out_probe = out_probe[:actual]
-        if track_build_matches:
-            return out_build, out_probe, matched
-        return out_build, out_probe
+            else:
+                g.join_probe_fill(bdesc.data_ptr(), btop.data_ptr(), pdesc.data_ptr(),
+                                  ptop.data_ptr(), len(pcols), nprobe,
+                                  self.slots.data_ptr(), self.capacity, counter.data_ptr(),
+                                  out_build, out_probe, capacity, matched, stream)
+        return self._gather_maps(launch, dev, out_hint, track_build_matches)
 
     def mark_matches(self, probe) -> torch.Tensor:
         """Stream the probe rows and return per-BUILD-row matched flags
@@ -505,6 +634,21 @@ def make_left_outer(probe_size: int, build_idx: torch.Tensor,
                                      device=dev)])
     lo_probe = torch.cat([probe_idx, unmatched])
     return lo_build, lo_probe
+
+
+def append_unmatched_build(build_matched: torch.Tensor,
+                           build_idx: torch.Tensor, probe_idx: torch.Tensor):
+    """Left-outer pairs to FULL OUTER: the build rows whose `build_matched`
+    flag is 0 follow the pairs, ascending, with probe index -1. Both results
+    are int64."""
+    from .compact import nonzero
+    unmatched_b = nonzero(build_matched == 0)
+    fo_build = torch.cat([build_idx.long(), unmatched_b])
+    fo_probe = torch.cat([probe_idx,
+                          torch.full((unmatched_b.numel(),), -1,
+                                     dtype=torch.int64,
+                                     device=probe_idx.device)])
+    return fo_build, fo_probe
 
 
 def make_full_outer(build_matched: torch.Tensor, build_idx: torch.Tensor,

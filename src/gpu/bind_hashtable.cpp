@@ -47,6 +47,27 @@ void srj_join_probe_d32(const void*, int32_t, const uint8_t*, int64_t,
                         const void*, int64_t, long long, uint64_t*, int32_t*,
                         int64_t*, int64_t, uint8_t*, int32_t, hipStream_t);
 int32_t srj_join_probe_tile(int32_t);
+void srj_join_probe_mode_i64(const long long*, const uint8_t*, int64_t,
+                             const void*, int64_t, uint64_t*, int32_t*,
+                             int64_t*, int64_t, uint8_t*, int32_t, int32_t,
+                             uint8_t*, int32_t, hipStream_t);
+void srj_join_probe_mode_n32(const void*, int32_t, const uint8_t*, int64_t,
+                             const void*, int64_t, long long, uint64_t*,
+                             int32_t*, int64_t*, int64_t, uint8_t*, int32_t,
+                             int32_t, uint8_t*, int32_t, hipStream_t);
+void srj_join_probe_mode_d32(const void*, int32_t, const uint8_t*, int64_t,
+                             const void*, int64_t, long long, uint64_t*,
+                             int32_t*, int64_t*, int64_t, uint8_t*, int32_t,
+                             int32_t, uint8_t*, int32_t, hipStream_t);
+}
+
+// mode of the join_probe_mode_* entry points (ProbeEmit in join_probe.hpp);
+// the inner probe has entry points of its own
+static void check_probe_mode(int32_t mode, uintptr_t probe_hit) {
+  if (mode != 1 && mode != 2)
+    throw std::invalid_argument("join probe mode must be 1 (outer) or 2 (flag)");
+  if (mode == 2 && !probe_hit)
+    throw std::invalid_argument("join probe mode 2 needs probe_hit");
 }
 
 void register_hashtable(py::module_& m) {
@@ -203,6 +224,53 @@ void register_hashtable(py::module_& m) {
                              as_ptr<uint8_t>(build_matched), fill,
                              as_stream(stream));
           check_hip("join_probe_d32");
+        });
+  m.def("join_probe_mode_i64",
+        [](uintptr_t probe, uintptr_t pvalid, int64_t nprobe, uintptr_t slots,
+           int64_t capacity, uintptr_t counter, uintptr_t out_build,
+           uintptr_t out_probe, int64_t out_capacity, uintptr_t build_matched,
+           int32_t fill, int32_t mode, uintptr_t probe_hit, int32_t anti,
+           uintptr_t stream) {
+          check_probe_mode(mode, probe_hit);
+          srj_join_probe_mode_i64(
+              as_ptr<long long>(probe), as_ptr<uint8_t>(pvalid), nprobe,
+              as_ptr<void>(slots), capacity, as_ptr<uint64_t>(counter),
+              as_ptr<int32_t>(out_build), as_ptr<int64_t>(out_probe),
+              out_capacity, as_ptr<uint8_t>(build_matched), fill, mode,
+              as_ptr<uint8_t>(probe_hit), anti, as_stream(stream));
+          check_hip("join_probe_mode_i64");
+        });
+  m.def("join_probe_mode_n32",
+        [](uintptr_t probe, int32_t key_i32, uintptr_t pvalid, int64_t nprobe,
+           uintptr_t slots, int64_t capacity, int64_t kmin, uintptr_t counter,
+           uintptr_t out_build, uintptr_t out_probe, int64_t out_capacity,
+           uintptr_t build_matched, int32_t fill, int32_t mode,
+           uintptr_t probe_hit, int32_t anti, uintptr_t stream) {
+          check_probe_mode(mode, probe_hit);
+          srj_join_probe_mode_n32(
+              as_ptr<void>(probe), key_i32, as_ptr<uint8_t>(pvalid), nprobe,
+              as_ptr<void>(slots), capacity, (long long)kmin,
+              as_ptr<uint64_t>(counter), as_ptr<int32_t>(out_build),
+              as_ptr<int64_t>(out_probe), out_capacity,
+              as_ptr<uint8_t>(build_matched), fill, mode,
+              as_ptr<uint8_t>(probe_hit), anti, as_stream(stream));
+          check_hip("join_probe_mode_n32");
+        });
+  m.def("join_probe_mode_d32",
+        [](uintptr_t probe, int32_t key_i32, uintptr_t pvalid, int64_t nprobe,
+           uintptr_t slots, int64_t range, int64_t kmin, uintptr_t counter,
+           uintptr_t out_build, uintptr_t out_probe, int64_t out_capacity,
+           uintptr_t build_matched, int32_t fill, int32_t mode,
+           uintptr_t probe_hit, int32_t anti, uintptr_t stream) {
+          check_probe_mode(mode, probe_hit);
+          srj_join_probe_mode_d32(
+              as_ptr<void>(probe), key_i32, as_ptr<uint8_t>(pvalid), nprobe,
+              as_ptr<void>(slots), range, (long long)kmin,
+              as_ptr<uint64_t>(counter), as_ptr<int32_t>(out_build),
+              as_ptr<int64_t>(out_probe), out_capacity,
+              as_ptr<uint8_t>(build_matched), fill, mode,
+              as_ptr<uint8_t>(probe_hit), anti, as_stream(stream));
+          check_hip("join_probe_mode_d32");
         });
   m.def("part_hist",
         [](uintptr_t keys, int64_t n, int32_t pbits, uintptr_t hist,

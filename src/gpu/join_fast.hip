@@ -296,6 +296,70 @@ struct DenseLayout {
 constexpr int DENSE_PPIPE = 8;
 constexpr int DENSE_BLOCK = 1024;
 
+// What a probe launch takes besides its keys and its table; the entry points
+// of a layout differ only in which of these they expose.
+struct ProbeOut {
+  uint64_t* counter;
+  int32_t* out_build;
+  int64_t* out_probe;
+  int64_t out_capacity;
+  uint8_t* build_matched;
+  int32_t fill;
+  const int32_t* idxmap;
+  ProbeEmit emit;
+  uint8_t* probe_hit;
+  int32_t anti;
+};
+
+template <typename L, int PPIPE, int BLOCK>
+static void probe_keys(const void* probe, int32_t key_i32,
+                       const uint8_t* pvalid, int64_t nprobe, L l,
+                       const ProbeOut& o, hipStream_t stream) {
+  if (key_i32)
+    launch_probe<L, int, PPIPE, BLOCK>(
+        reinterpret_cast<const int*>(probe), pvalid, nprobe, l, o.counter,
+        o.out_build, o.out_probe, o.out_capacity, o.build_matched, o.fill,
+        o.idxmap, stream, o.emit, o.probe_hit, o.anti);
+  else
+    launch_probe<L, long long, PPIPE, BLOCK>(
+        reinterpret_cast<const long long*>(probe), pvalid, nprobe, l,
+        o.counter, o.out_build, o.out_probe, o.out_capacity, o.build_matched,
+        o.fill, o.idxmap, stream, o.emit, o.probe_hit, o.anti);
+}
+
+// batch 16 measured slower for the wide table (12.5 vs 15.8 B rows/s):
+// occupancy drop
+static void probe_wide(const long long* probe, const uint8_t* pvalid,
+                       int64_t nprobe, const void* slots, int64_t capacity,
+                       const ProbeOut& o, hipStream_t stream) {
+  WideLayout l{reinterpret_cast<const longlong2*>(slots),
+               (uint64_t)(capacity - 1)};
+  launch_probe<WideLayout, long long, PIPE, DEFAULT_BLOCK>(
+      probe, pvalid, nprobe, l, o.counter, o.out_build, o.out_probe,
+      o.out_capacity, o.build_matched, o.fill, o.idxmap, stream, o.emit,
+      o.probe_hit, o.anti);
+}
+
+static void probe_narrow(const void* probe, int32_t key_i32,
+                         const uint8_t* pvalid, int64_t nprobe,
+                         const void* slots, int64_t capacity, long long kmin,
+                         const ProbeOut& o, hipStream_t stream) {
+  NarrowLayout l{reinterpret_cast<const unsigned long long*>(slots),
+                 (uint64_t)(capacity - 1), kmin};
+  probe_keys<NarrowLayout, PIPE, DEFAULT_BLOCK>(probe, key_i32, pvalid,
+                                                nprobe, l, o, stream);
+}
+
+static void probe_dense(const void* probe, int32_t key_i32,
+                        const uint8_t* pvalid, int64_t nprobe,
+                        const void* slots, int64_t range, long long kmin,
+                        const ProbeOut& o, hipStream_t stream) {
+  DenseLayout l{reinterpret_cast<const uint32_t*>(slots), (uint64_t)range,
+                kmin};
+  probe_keys<DenseLayout, DENSE_PPIPE, DENSE_BLOCK>(probe, key_i32, pvalid,
+                                                    nprobe, l, o, stream);
+}
+
 }  // namespace srj
 
 using namespace srj;
@@ -315,18 +379,33 @@ void srj_join_build_i64(const long long* keys, const uint8_t* valid, int64_t nro
       (uint64_t)(capacity - 1));
 }
 
-// batch 16 measured slower for the wide table (12.5 vs 15.8 B rows/s):
-// occupancy drop
 void srj_join_probe_i64(const long long* probe, const uint8_t* pvalid,
                         int64_t nprobe, const void* slots, int64_t capacity,
                         uint64_t* counter, int32_t* out_build, int64_t* out_probe,
                         int64_t out_capacity, uint8_t* build_matched, int32_t fill,
                         const int32_t* idxmap, hipStream_t stream) {
-  WideLayout l{reinterpret_cast<const longlong2*>(slots),
-               (uint64_t)(capacity - 1)};
-  launch_probe<WideLayout, long long, PIPE, DEFAULT_BLOCK>(
-      probe, pvalid, nprobe, l, counter, out_build, out_probe, out_capacity,
-      build_matched, fill, idxmap, stream);
+  probe_wide(probe, pvalid, nprobe, slots, capacity,
+             {counter, out_build, out_probe, out_capacity, build_matched, fill,
+              idxmap, ProbeEmit::INNER, nullptr, 0},
+             stream);
+}
+
+// The emit modes of join_probe.hpp on the same tables. mode: 1 left outer
+// (build index -1 for an unmatched probe row, counted too), 2 flags:
+// probe_hit[row] = has_match ^ anti, and nothing else is written. probe_hit
+// is 8-byte aligned and has (nprobe + 15) / 16 * 16 bytes: the hashed layouts
+// store 8 flags as one word. The bindings pass no other mode.
+void srj_join_probe_mode_i64(const long long* probe, const uint8_t* pvalid,
+                             int64_t nprobe, const void* slots,
+                             int64_t capacity, uint64_t* counter,
+                             int32_t* out_build, int64_t* out_probe,
+                             int64_t out_capacity, uint8_t* build_matched,
+                             int32_t fill, int32_t mode, uint8_t* probe_hit,
+                             int32_t anti, hipStream_t stream) {
+  probe_wide(probe, pvalid, nprobe, slots, capacity,
+             {counter, out_build, out_probe, out_capacity, build_matched, fill,
+              nullptr, (ProbeEmit)mode, probe_hit, anti},
+             stream);
 }
 
 // key_i32 != 0: keys are a 4-byte int column read in place, else int64
@@ -351,18 +430,24 @@ void srj_join_probe_n32(const void* probe, int32_t key_i32,
                         int64_t out_capacity, uint8_t* build_matched,
                         int32_t fill, const int32_t* idxmap,
                         hipStream_t stream) {
-  NarrowLayout l{reinterpret_cast<const unsigned long long*>(slots),
-                 (uint64_t)(capacity - 1), kmin};
-  if (key_i32)
-    launch_probe<NarrowLayout, int, PIPE, DEFAULT_BLOCK>(
-        reinterpret_cast<const int*>(probe), pvalid, nprobe, l, counter,
-        out_build, out_probe, out_capacity, build_matched, fill, idxmap,
-        stream);
-  else
-    launch_probe<NarrowLayout, long long, PIPE, DEFAULT_BLOCK>(
-        reinterpret_cast<const long long*>(probe), pvalid, nprobe, l, counter,
-        out_build, out_probe, out_capacity, build_matched, fill, idxmap,
-        stream);
+  probe_narrow(probe, key_i32, pvalid, nprobe, slots, capacity, kmin,
+               {counter, out_build, out_probe, out_capacity, build_matched,
+                fill, idxmap, ProbeEmit::INNER, nullptr, 0},
+               stream);
+}
+
+void srj_join_probe_mode_n32(const void* probe, int32_t key_i32,
+                             const uint8_t* pvalid, int64_t nprobe,
+                             const void* slots, int64_t capacity,
+                             long long kmin, uint64_t* counter,
+                             int32_t* out_build, int64_t* out_probe,
+                             int64_t out_capacity, uint8_t* build_matched,
+                             int32_t fill, int32_t mode, uint8_t* probe_hit,
+                             int32_t anti, hipStream_t stream) {
+  probe_narrow(probe, key_i32, pvalid, nprobe, slots, capacity, kmin,
+               {counter, out_build, out_probe, out_capacity, build_matched,
+                fill, nullptr, (ProbeEmit)mode, probe_hit, anti},
+               stream);
 }
 
 // slots: `range` zeroed words; flag: one zeroed word (see the kernel).
@@ -389,18 +474,24 @@ void srj_join_probe_d32(const void* probe, int32_t key_i32,
                         int64_t* out_probe, int64_t out_capacity,
                         uint8_t* build_matched, int32_t fill,
                         hipStream_t stream) {
-  DenseLayout l{reinterpret_cast<const uint32_t*>(slots), (uint64_t)range,
-                kmin};
-  if (key_i32)
-    launch_probe<DenseLayout, int, DENSE_PPIPE, DENSE_BLOCK>(
-        reinterpret_cast<const int*>(probe), pvalid, nprobe, l, counter,
-        out_build, out_probe, out_capacity, build_matched, fill, nullptr,
-        stream);
-  else
-    launch_probe<DenseLayout, long long, DENSE_PPIPE, DENSE_BLOCK>(
-        reinterpret_cast<const long long*>(probe), pvalid, nprobe, l, counter,
-        out_build, out_probe, out_capacity, build_matched, fill, nullptr,
-        stream);
+  probe_dense(probe, key_i32, pvalid, nprobe, slots, range, kmin,
+              {counter, out_build, out_probe, out_capacity, build_matched,
+               fill, nullptr, ProbeEmit::INNER, nullptr, 0},
+              stream);
+}
+
+void srj_join_probe_mode_d32(const void* probe, int32_t key_i32,
+                             const uint8_t* pvalid, int64_t nprobe,
+                             const void* slots, int64_t range, long long kmin,
+                             uint64_t* counter, int32_t* out_build,
+                             int64_t* out_probe, int64_t out_capacity,
+                             uint8_t* build_matched, int32_t fill,
+                             int32_t mode, uint8_t* probe_hit, int32_t anti,
+                             hipStream_t stream) {
+  probe_dense(probe, key_i32, pvalid, nprobe, slots, range, kmin,
+              {counter, out_build, out_probe, out_capacity, build_matched,
+               fill, nullptr, (ProbeEmit)mode, probe_hit, anti},
+              stream);
 }
 
 }  // extern "C"

@@ -34,6 +34,28 @@
 //  * idxmap (may be null; chained layouts only) holds the source rows of
 //    partitioned probe keys and replaces the row number in out_probe.
 //
+// What a probe emits is a compile-time mode, ProbeEmit. INNER is all of the
+// above. The other two sit under `if constexpr`, so the INNER kernels are
+// the code they were without them:
+//  * OUTER (count and FILL): the left outer join. A row of [0, nprobe) that
+//    resolve leaves without a match (null key, key that cannot be in the
+//    table, or no match) becomes one pair of its own: its `hit` bit is set,
+//    it counts 1 and its first-match register stays 0, so emit stores build
+//    index 0 - 1 = -1 for it. emit leaves build_matched alone for such a
+//    pair: there is no build row -1. The counter receives matching pairs
+//    plus unmatched probe rows; reservation and capacity rules are INNER's.
+//    idxmap is not supported (pass null).
+//  * FLAG: one byte per probe row, probe_hit[row] = has_match ^ anti, and
+//    nothing else: no counter, no LDS, no barrier, no atomic, no output
+//    pairs, no build_matched. A chain walk ends at the first match. A null or
+//    dead key has has_match = 0. probe_hit is 8-byte aligned and has
+//    (nprobe + 15) / 16 * 16 bytes; every byte below nprobe is written, bytes
+//    from nprobe up to the next multiple of 8 may be (with 0), nothing
+//    beyond. A chained layout stores a lane's 8 consecutive flags as one
+//    8-byte word at probe_hit + base, base a multiple of 8 (hence the
+//    alignment rule), the interleaved layout one byte per b, a contiguous
+//    run per wave.
+//
 // A layout L is passed by value: the slot pointer, `mask` or `range`, and
 // `kmin` where it has one. It supplies only what differs between the tables:
 //   Tag     what a lane keeps per row to compare against slot words
@@ -48,12 +70,25 @@
 //                 interleaved rows, and next, reindex and chain are not needed
 //   WG_APPEND     one reservation per workgroup and tile (see above)
 #pragma once
+#include <type_traits>
+
 #include "srj_common.hpp"
 
 namespace srj {
 
+// what a probe emits (see above); the values are the entry points' `mode`
+enum class ProbeEmit : int32_t { INNER = 0, OUTER = 1, FLAG = 2 };
+
+// bit b of an 8-bit mask to byte b of a word: 8 flag bytes, one store
+__device__ inline uint64_t bits_to_bytes(uint32_t m) {
+  uint32_t lo = (m & 1u) | (m & 2u) << 7 | (m & 4u) << 14 | (m & 8u) << 21;
+  m >>= 4;
+  uint32_t hi = (m & 1u) | (m & 2u) << 7 | (m & 4u) << 14 | (m & 8u) << 21;
+  return (uint64_t)hi << 32 | lo;
+}
+
 template <typename L, typename K, bool FILL, bool HAS_VALID, int PPIPE,
-          int BLOCK>
+          int BLOCK, ProbeEmit EMIT = ProbeEmit::INNER>
 __global__ void __launch_bounds__(BLOCK, (PPIPE == 8 && !L::CHAINED) ? 8 : 1)
 join_probe_kernel_t(const K* __restrict__ probe,
                     const uint8_t* __restrict__ pvalid, int64_t nprobe,
@@ -61,9 +96,13 @@ join_probe_kernel_t(const K* __restrict__ probe,
                     int32_t* __restrict__ out_build,
                     int64_t* __restrict__ out_probe, int64_t out_capacity,
                     uint8_t* __restrict__ build_matched,
-                    const int32_t* __restrict__ idxmap) {
+                    const int32_t* __restrict__ idxmap,
+                    uint8_t* __restrict__ probe_hit, uint32_t anti) {
   static_assert(PPIPE == 8 || PPIPE == 16, "validity bytes per batch");
   static_assert(L::WG_APPEND || L::CHAINED, "b-major needs the LDS table");
+  static_assert(EMIT != ProbeEmit::FLAG || !FILL, "FLAG has no count or fill");
+  constexpr bool OUTER = EMIT == ProbeEmit::OUTER;
+  constexpr bool FLAG = EMIT == ProbeEmit::FLAG;
   using Tag = typename L::Tag;
   using Word = typename L::Word;
   constexpr bool ROWMAJOR = !L::CHAINED;
@@ -84,6 +123,8 @@ join_probe_kernel_t(const K* __restrict__ probe,
     const int64_t tbase = tile * TILE;
     const int64_t base = tbase + (int64_t)threadIdx.x * (ROWMAJOR ? 1 : PPIPE);
     uint32_t vbits = (1u << PPIPE) - 1u;
+    // OUTER, FLAG: rows inside [0, nprobe), which vbits folds into "valid"
+    [[maybe_unused]] uint32_t inb = (1u << PPIPE) - 1u;
     K k[PPIPE];
     if (ROWMAJOR) {
       uint32_t vb[PPIPE];
@@ -104,6 +145,8 @@ join_probe_kernel_t(const K* __restrict__ probe,
           k[b] = probe[crow];
           vb[b] = HAS_VALID ? (uint32_t)pvalid[crow >> 3] >> (crow & 7) : 1u;
           if (row >= nprobe) vb[b] = 0;
+          if constexpr (OUTER || FLAG)
+            if (row >= nprobe) inb &= ~(1u << b);
         }
       }
       vbits = 0;
@@ -119,6 +162,8 @@ join_probe_kernel_t(const K* __restrict__ probe,
       if (base + PPIPE > nprobe) {
         int64_t tail = nprobe - base;
         vbits &= (uint32_t)((1u << (tail < 0 ? 0 : tail)) - 1u);
+        if constexpr (OUTER || FLAG)
+          inb = (uint32_t)((1u << (tail < 0 ? 0 : tail)) - 1u);
       }
 #pragma unroll
       for (int b = 0; b < PPIPE; ++b) {
@@ -138,6 +183,46 @@ join_probe_kernel_t(const K* __restrict__ probe,
       }
 #pragma unroll
       for (int b = 0; b < PPIPE; ++b) fw[b] = layout.load(s[b]);
+    }
+    if constexpr (FLAG) {
+      // has_match alone: a chain walk ends at the first match
+      uint32_t hit = 0;
+#pragma unroll
+      for (int b = 0; b < PPIPE; ++b) {
+        if (!((vbits >> b) & 1) || L::empty(fw[b])) continue;
+        bool m = L::match(fw[b], tag[b]);
+        if constexpr (L::CHAINED) {
+          if (!m && L::chain(fw[b])) {
+            auto sl = layout.reindex(tag[b]);
+            while (true) {
+              sl = layout.next(sl);
+              Word w = layout.load(sl);
+              if (L::empty(w)) break;
+              m = L::match(w, tag[b]);
+              if (m || !L::chain(w)) break;
+            }
+          }
+        }
+        hit |= (uint32_t)m << b;
+      }
+      // rows past nprobe get 0 whatever anti is
+      const uint32_t flags = (hit ^ (anti ? ~0u : 0u)) & inb;
+      if constexpr (ROWMAJOR) {
+#pragma unroll
+        for (int b = 0; b < PPIPE; ++b)
+          if ((inb >> b) & 1)
+            probe_hit[base + b * STEP] = (uint8_t)((flags >> b) & 1u);
+      } else {
+        // probe_hit is 8-byte aligned, base is a multiple of 8 and the
+        // buffer is padded to 16: a word that starts below nprobe is aligned
+        // and ends inside the buffer
+#pragma unroll
+        for (int w = 0; w < PPIPE / 8; ++w)
+          if (base + 8 * w < nprobe)
+            *reinterpret_cast<uint64_t*>(probe_hit + base + 8 * w) =
+                bits_to_bytes((flags >> (8 * w)) & 0xffu);
+      }
+      continue;
     }
     // per row: bit of `hit` = has a match, bit of `multi` = has several
     uint32_t nm = 0, hit = 0, multi = 0;
@@ -170,6 +255,12 @@ join_probe_kernel_t(const K* __restrict__ probe,
       hit |= (uint32_t)(n != 0) << b;
       multi |= (uint32_t)(n > 1) << b;
       nm += n;
+    }
+    if constexpr (OUTER) {
+      // an unmatched row inside is a pair of its own; its hit1 is still 0
+      const uint32_t lone = inb & ~hit;
+      hit |= lone;
+      nm += (uint32_t)__popc(lone);
     }
     if (!FILL) {
       count_local += nm;
@@ -246,7 +337,8 @@ join_probe_kernel_t(const K* __restrict__ probe,
             out_build[pos] = (int32_t)(r1 - 1);
             out_probe[pos] = prow;
           }
-          if (build_matched) build_matched[r1 - 1] = 1;
+          // OUTER: r1 == 0 is an unmatched probe row, build index -1
+          if (build_matched && (!OUTER || r1)) build_matched[r1 - 1] = 1;
           ++pos;
         };
         if constexpr (L::CHAINED) {
@@ -271,39 +363,51 @@ join_probe_kernel_t(const K* __restrict__ probe,
       }
     }
   }
-  if (!FILL) {
+  if (!FILL && !FLAG) {
     count_local = wave_sum(count_local);
     if (lane == 0 && count_local)
       atomicAdd((unsigned long long*)counter, (unsigned long long)count_local);
   }
 }
 
-// The one fill x validity ladder. Count mode passes null outputs.
+// The one emit x fill x validity ladder. Count mode passes null outputs;
+// FLAG writes probe_hit alone and ignores fill.
 template <typename L, typename K, int PPIPE, int BLOCK>
 void launch_probe(const K* probe, const uint8_t* pvalid, int64_t nprobe,
                   L layout, uint64_t* counter, int32_t* out_build,
                   int64_t* out_probe, int64_t out_capacity,
                   uint8_t* build_matched, int32_t fill, const int32_t* idxmap,
-                  hipStream_t stream) {
-  auto kernel =
-      fill ? (pvalid ? join_probe_kernel_t<L, K, true, true, PPIPE, BLOCK>
-                     : join_probe_kernel_t<L, K, true, false, PPIPE, BLOCK>)
-           : (pvalid ? join_probe_kernel_t<L, K, false, true, PPIPE, BLOCK>
-                     : join_probe_kernel_t<L, K, false, false, PPIPE, BLOCK>);
-  if (!fill) {
+                  hipStream_t stream, ProbeEmit emit = ProbeEmit::INNER,
+                  uint8_t* probe_hit = nullptr, int32_t anti = 0) {
+  constexpr ProbeEmit I = ProbeEmit::INNER, O = ProbeEmit::OUTER,
+                      F = ProbeEmit::FLAG;
+  auto pick = [&](auto with_valid) {
+    constexpr bool V = decltype(with_valid)::value;
+    if (emit == F) return join_probe_kernel_t<L, K, false, V, PPIPE, BLOCK, F>;
+    if (emit == O)
+      return fill ? join_probe_kernel_t<L, K, true, V, PPIPE, BLOCK, O>
+                  : join_probe_kernel_t<L, K, false, V, PPIPE, BLOCK, O>;
+    return fill ? join_probe_kernel_t<L, K, true, V, PPIPE, BLOCK, I>
+                : join_probe_kernel_t<L, K, false, V, PPIPE, BLOCK, I>;
+  };
+  auto kernel = pvalid ? pick(std::true_type{}) : pick(std::false_type{});
+  if (!fill || emit == F) {
     out_build = nullptr;
     out_probe = nullptr;
     out_capacity = 0;
     build_matched = nullptr;
     idxmap = nullptr;
   }
+  if (emit != I) idxmap = nullptr;
+  if (emit != F) probe_hit = nullptr;
   // one tile of BLOCK * PPIPE rows per workgroup and iteration; the cap
   // keeps MAX_GRID * DEFAULT_BLOCK threads whatever the workgroup size
   kernel<<<grid_1d((nprobe + PPIPE - 1) / PPIPE, BLOCK,
                    MAX_GRID * DEFAULT_BLOCK / BLOCK),
            BLOCK, 0, stream>>>(probe, pvalid, nprobe, layout, counter,
                                out_build, out_probe, out_capacity,
-                               build_matched, idxmap);
+                               build_matched, idxmap, probe_hit,
+                               (uint32_t)(anti != 0));
 }
 
 }  // namespace srj
