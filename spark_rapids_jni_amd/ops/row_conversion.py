@@ -1,9 +1,12 @@
 """JCUDF row <-> columnar conversion (Java API parity: RowConversion.java).
 
 Layout per RowConversion.java:59-101: columns packed in order, each aligned
-to its width; validity bytes (bit c%8 of byte c/8, set = valid) right after
-the last column; row size padded to 8 bytes. Output batched so each batch
-stays under 2GB (reference row_conversion.cu batching).
+to its own size (DECIMAL128 to 16); validity bytes (bit c%8 of byte c/8,
+set = valid) right after the last column; row size padded to 8 bytes.
+Padding and the slots of null columns are zero. Output batched so each
+batch stays under 2GB (reference row_conversion.cu batching).
+tests/test_rowconv_jcudf.py restates the rule independently and checks both
+directions byte for byte against it.
 """
 import struct
 from typing import List, Tuple
@@ -18,13 +21,16 @@ MAX_BATCH_BYTES = 2**31 - 8
 
 
 def row_layout(dtypes: List[DType]) -> Tuple[List[int], int, int]:
-    """Returns (per-column row offsets, validity_off, row_size)."""
+    """Returns (per-column row offsets, validity_off, row_size).
+
+    Each column is aligned to its own size (1/2/4/8/16 bytes), one validity
+    bit per column follows the last column without padding, and the row is
+    padded to a multiple of 8 bytes."""
     off = 0
     offs = []
     for dt in dtypes:
         w = FIXED_WIDTH[dt]
-        a = min(w, 8)
-        off = (off + a - 1) // a * a
+        off = (off + w - 1) // w * w
         offs.append(off)
         off += w
     validity_off = off
@@ -71,7 +77,7 @@ def convert_to_rows(table: Table) -> List[Tuple[torch.Tensor, int]]:
                 c.validity[start // 8:] if c.validity is not None else None,
                 scale=c.scale))
         # zeros: padding bytes are part of the format contract
-        buf = torch.zeros(max(m * row_size, 1), dtype=torch.uint8, device=dev)
+        buf = torch.zeros(m * row_size, dtype=torch.uint8, device=dev)
         desc = _pack_desc(views, offs, dev)
         g.to_rows(desc.data_ptr(), len(cols), m, row_size, validity_off,
                   buf.data_ptr(), stream)
@@ -123,21 +129,24 @@ def convert_from_rows(batches: List[Tuple[torch.Tensor, int]],
 
 def var_row_layout(dtypes: List[DType]) -> Tuple[List[int], int, int]:
     """(per-column fixed-section offsets, validity_off, fixed_size).
-    STRING columns take an 8-byte (offset,len) slot aligned to 4."""
+
+    STRING columns take an 8-byte (offset,len) slot aligned to 4; every
+    other column is aligned to its own size. fixed_size is the UNPADDED end
+    of the validity bytes: the chars of a row start there, in column order,
+    and the row takes round_up(fixed_size + its string bytes, 8) bytes."""
     off = 0
     offs = []
     for dt in dtypes:
         if dt == DType.STRING:
             w, a = 8, 4
         else:
-            w = FIXED_WIDTH[dt]
-            a = min(w, 8)
+            w = a = FIXED_WIDTH[dt]
         off = (off + a - 1) // a * a
         offs.append(off)
         off += w
     validity_off = off
     off += (len(dtypes) + 7) // 8
-    return offs, validity_off, (off + 7) // 8 * 8
+    return offs, validity_off, off
 
 
 def _pack_desc_var(cols: List[Column], offs, dev):

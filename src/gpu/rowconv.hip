@@ -3,15 +3,26 @@
 // Reference parity: RowConversion.java:35-158 + row_conversion.cu (2,626 LoC,
 // the reference's largest kernel file). Row layout (RowConversion.java:59-101):
 // each row is a C-struct-like packing of the columns in order (each column
-// aligned to its width), validity bytes (1 per 8 columns, bit i%8 of byte
-// i/8, set = valid) immediately after the last column, row padded to 8 bytes.
+// aligned to its own size, DECIMAL128 to 16; a string is an 8-byte
+// (offset-in-row, length) slot aligned to 4), validity bytes (1 per 8
+// columns, bit i%8 of byte i/8, set = valid) immediately after the last
+// column, row padded to 8 bytes. Padding and null slots are zero. A
+// variable-width row holds its chars from the UNPADDED end of the validity
+// bytes on and is padded to 8 after them. The layout itself is computed by
+// ops/row_conversion.py; the kernels take offsets and sizes as arguments and
+// access rows in pieces of at most 8 bytes, since a row is only 8-aligned.
 //
-// MI355X design: one thread per row; column loads are coalesced (consecutive
-// lanes read consecutive rows); row-major writes go through L2 (64B lines
-// amortize across a wave's 64 adjacent rows when row_size is small, the
-// common Spark UDF case). A future LDS-tiled variant can stage 64x row_size
-// tiles for fully-coalesced stores (reference copy_to_rows tile design);
-// correctness and API shape come first.
+// Kernels: to-rows LDS-tiled (64-row tiles) when a tile fits 64 KB of LDS,
+// else one thread per row; from-rows LDS-tiled at the largest of 256/128/64
+// rows that fits (SRJ_FROM_ROWS_TILE overrides), else one thread per row;
+// three one-thread-per-row kernels for the variable-width path. Validity
+// masks are written as whole 64-bit words, never past ceil(nrows/64) words.
+// nrows == 0 launches nothing.
+//
+// tests/test_rowconv_jcudf.py checks every one of these kernels byte for
+// byte against a host packer written from the format's rule: both sides of
+// each dispatch boundary, grid-stride second laps, batch seams, and guard
+// bands round every output buffer.
 #include "srj_common.hpp"
 
 namespace srj {
@@ -313,6 +324,10 @@ __global__ void from_rows_tiled_kernel(const RowColDesc* __restrict__ cols,
       for (int32_t cs = wave; cs < ncols * nsub; cs += nwaves) {
         int32_t c = cs / nsub;
         int32_t sub = cs % nsub;
+        // a subtile past the last row has no validity word to write: the
+        // mask ends at ceil(nrows/64) words (wave-uniform, so the ballot
+        // below stays whole-wave)
+        if (sub * WAVE >= m) continue;
         int32_t r = sub * WAVE + lane;
         bool in_range = r < m;
         const uint8_t* src = tile + (int64_t)(in_range ? r : 0) * pitch;
@@ -467,6 +482,7 @@ extern "C" {
 
 void srj_to_rows(const void* cols, int32_t ncols, int64_t nrows, int32_t row_size,
                  int32_t validity_off, uint8_t* out, hipStream_t stream) {
+  if (nrows <= 0) return;  // empty table: a zero-block launch is an error
   int32_t pitch = ((row_size >> 2) & 1) ? row_size : row_size + 4;
   size_t lds = (size_t)TILE_ROWS * pitch;
   if (lds <= 64 * 1024) {
@@ -486,6 +502,7 @@ void srj_to_rows(const void* cols, int32_t ncols, int64_t nrows, int32_t row_siz
 void srj_from_rows(const void* cols, int32_t ncols, int64_t nrows,
                    int32_t row_size, int32_t validity_off, const uint8_t* in,
                    hipStream_t stream) {
+  if (nrows <= 0) return;  // empty batch: a zero-block launch is an error
   // biggest tile whose LDS fits 64 KB: larger tiles give longer
   // per-column write bursts (SRJ_FROM_ROWS_TILE overrides for tuning)
   int tr = 0;

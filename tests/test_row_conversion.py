@@ -97,7 +97,7 @@ def test_var_row_layout():
     offs, voff, fixed = var_row_layout([DType.INT64, DType.STRING, DType.INT8])
     assert offs == [0, 8, 16]
     assert voff == 17
-    assert fixed == 24
+    assert fixed == 18
 
 
 @pytest.mark.gpu
@@ -140,6 +140,6 @@ def test_var_row_layout_bytes():
     i32, spos, slen = struct.unpack_from("<i", r0, offs[0])[0], \
         struct.unpack_from("<ii", r0, offs[1])[0], \
         struct.unpack_from("<ii", r0, offs[1])[1]
-    assert i32 == 7 and spos == fixed and slen == 3
+    assert i32 == 7 and spos == 13 and slen == 3
     assert r0[spos:spos + 3] == b"abc"
     assert r0[voff] == 0b11
