@@ -275,6 +275,83 @@ def window_bench(n, dev, g):
                 "ms_max": round(xs[-1] * 1e3, 4)}), flush=True)
 
 
+def window_rolling_bench(n, part_rows, dev, g):
+    """lag(1) and sum / max over bounded ROWS frames: window_tensors against
+    the torch expression a caller can write today (the CPU twin of
+    ops/window.py on CUDA tensors: one shifted, masked read per offset), and
+    the kernel's staged path against its direct path at the same width. Both
+    sides start from the same sort order and flags; the sort is not timed."""
+    from spark_rapids_jni_amd.ops import window as W
+    from spark_rapids_jni_amd.ops.sort import (key_change_flags,
+                                               sort_order_tensors)
+    H = W.ROLL_MAX_REACH
+    env = "SRJ_WINDOW_ROLLING_DIRECT"
+    os.environ.pop(env, None)
+    pk = torch.randint(0, max(1, n // part_rows), (n,), device=dev,
+                       generator=g)
+    ok = torch.randint(0, 2**40, (n,), device=dev, generator=g)
+    vdata = torch.randint(-400, 400, (n,), device=dev,
+                          generator=g).to(torch.float64) / 4
+    vvalid = torch.rand(n, device=dev, generator=g) < 0.9
+    perm = sort_order_tensors([pk, ok])
+    bnd = key_change_flags([pk], perm)
+    head = bnd != 0
+    head[0] = True
+
+    def native(funcs):
+        return W.window_tensors(perm, bnd, funcs)[0][0]
+
+    def direct(funcs):
+        os.environ[env] = "1"
+        try:
+            return native(funcs)
+        finally:
+            del os.environ[env]
+
+    def twin(funcs):
+        fs = W._check_funcs(funcs, n, perm.device, False)
+        return W._rolling_cpu(perm, head, fs)[0][0]
+
+    def record(name, width, a, b, fa, fb):
+        # both have run once (the equality check): size the timed window,
+        # and spend no warm-up calls on a case that takes seconds
+        slow = max(timeit(fa, 1, warmup=0), timeit(fb, 1, warmup=0))
+        reps = 7 if slow < 0.5 else 3
+        inner = 10 if slow < 0.005 else 1
+        a_s, b_s = [], []
+        for _ in range(reps):  # alternating, as ab_time
+            a_s.append(timeit(fa, inner, warmup=2 if slow < 0.5 else 0))
+            b_s.append(timeit(fb, inner, warmup=2 if slow < 0.5 else 0))
+        for path, xs in ((a, a_s), (b, b_s)):
+            xs = sorted(xs)
+            print(json.dumps({
+                "bench": "window_rolling_" + name, "path": path, "rows": n,
+                "partition_rows": part_rows, "width": width, "repeats": reps,
+                "calls_per_repeat": inner,
+                "ms": round(xs[len(xs) // 2] * 1e3, 4),
+                "ms_min": round(xs[0] * 1e3, 4),
+                "ms_max": round(xs[-1] * 1e3, 4)}), flush=True)
+
+    def frame(width):
+        return ("rows", -(width // 2), width // 2)
+
+    cases = [("lag", 1, [("lag", vdata, vvalid, 1)])]
+    for width in (3, 9, 33, 2 * H + 3):
+        for fn in ("sum", "max"):
+            cases.append((fn, width, [(fn, vdata, vvalid, frame(width))]))
+    for name, width, funcs in cases:
+        # the twin folds in the kernel's order: the same bits
+        assert torch.equal(native(funcs), twin(funcs)), (name, width)
+        record(name, width, "hip", "torch_twin", lambda: native(funcs),
+               lambda: twin(funcs))
+    for width in (3, 9, 33, 257, 2 * H + 1):
+        for fn in ("sum", "max"):
+            funcs = [(fn, vdata, vvalid, frame(width))]
+            assert torch.equal(native(funcs), direct(funcs)), (fn, width)
+            record(fn + "_paths", width, "staged", "direct",
+                   lambda: native(funcs), lambda: direct(funcs))
+
+
 def expr_bench(n, dev, g):
     """NDS eval_expr on the fused expression kernel against the same
     eval_expr forced to its torch evaluator, alternating in one process:
@@ -568,10 +645,19 @@ def main():
     ap.add_argument("--iters", type=int, default=5)
     ap.add_argument("--only", choices=["sort_order", "join_narrow",
                                       "join_dense", "join_modes", "window",
-                                      "expr", "groupby_sorted"],
+                                      "window_rolling", "expr",
+                                      "groupby_sorted"],
                     default=None,
                     help="run just this group")
     args = ap.parse_args()
+    if args.only == "window_rolling":
+        g = torch.Generator(device="cuda")
+        g.manual_seed(7)
+        # 2^20 and 2^24 rows; --rows N measures N rows alone
+        for wn in ((2**20, 2**24) if args.rows == 2**24 else (args.rows,)):
+            for part_rows in (1024, 16):
+                window_rolling_bench(wn, part_rows, "cuda", g)
+        return
     if args.only == "groupby_sorted":
         g = torch.Generator(device="cuda")
         g.manual_seed(7)

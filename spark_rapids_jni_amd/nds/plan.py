@@ -73,9 +73,10 @@ class Agg(Plan):
 class Window(Plan):
     child: Plan
     partition: List[str]
-    funcs: List[tuple]  # (out_name, fn, arg_col|None, order|None)
-    # fn: rank dense_rank row_number sum avg min max cumsum
-    # order: list of (col, asc) — required for rank-like and cumsum
+    funcs: List[tuple]  # (out_name, fn, arg_col|None, order|None[, k])
+    # fn: rank dense_rank row_number sum avg min max cumsum lag lead
+    # order: list of (col, asc) — required for rank-like, cumsum, lag, lead
+    # k: rows back (lag) / ahead (lead), default 1
 
 
 @dataclass
@@ -628,6 +629,9 @@ _WINDOW_FUNCS = {
     "dense_rank": ("dense_rank", "rows"),
     "row_number": ("row_number", "rows"),
 }
+# (name, "lag" | "lead", arg, order, k = 1): the value of arg k rows before /
+# after in the partition's order, a Val(data, valid) in the dtype of arg
+_WINDOW_SHIFTS = ("lag", "lead")
 # what the torch expression leaves where a frame holds no valid value
 _WINDOW_NULL_FILL = {"sum": 0.0, "cumsum": 0.0, "avg": 0.0,
                      "min": float("inf"), "max": float("-inf")}
@@ -1195,6 +1199,22 @@ class Engine:
                                                     as_tuple=False).view(-1)]
                         res_sorted = dr - seg_base[seg] + 1
                 out[name] = Val(res_sorted[inv])
+            elif fn in ("lag", "lead"):
+                assert order, f"{fn} needs an order"
+                k = spec[4] if len(spec) > 4 else 1
+                v = f.cols[arg]
+                idx = torch.arange(n, dtype=torch.int64, device=dev)
+                src = idx + (k if fn == "lead" else -k)
+                seg_end = torch.full((nseg,), n - 1, dtype=torch.int64,
+                                     device=dev)
+                seg_end[:-1] = seg_start[1:] - 1
+                ok = (src >= seg_start[seg]) & (src <= seg_end[seg])
+                src = src.clamp(0, n - 1)
+                if v.valid is not None:
+                    ok = ok & v.valid[perm][src]
+                data = v.data[perm][src]
+                data = torch.where(ok, data, torch.zeros_like(data))
+                out[name] = Val(data[inv], ok[inv], v.dict)
             else:
                 raise ValueError(fn)
         return Frame(out, n, f.sharded)
@@ -1210,7 +1230,7 @@ class Engine:
         dev = self.device
         groups: Dict[tuple, List[tuple]] = {}
         for spec in p.funcs:
-            if spec[1] not in _WINDOW_FUNCS:
+            if spec[1] not in _WINDOW_FUNCS and spec[1] not in _WINDOW_SHIFTS:
                 raise ValueError(spec[1])
             order = spec[3] if len(spec) > 3 else None
             key = tuple((c, bool(asc)) for c, asc in order) if order else ()
@@ -1232,6 +1252,12 @@ class Engine:
             funcs = []
             for spec in specs:
                 fn, arg = spec[1], spec[2]
+                if fn in _WINDOW_SHIFTS:
+                    assert key, f"{fn} needs an order"
+                    v = f.cols[arg]
+                    funcs.append((fn, v.data, v.valid,
+                                  spec[4] if len(spec) > 4 else 1))
+                    continue
                 wfn, frame = _WINDOW_FUNCS[fn]
                 if fn in ("rank", "dense_rank", "row_number"):
                     assert key, f"{fn} needs an order"
@@ -1246,6 +1272,10 @@ class Engine:
                     funcs.append((wfn, as_f64[arg], v.valid, frame))
             for spec, (data, valid) in zip(
                     specs, window_tensors(perm, part, funcs, peer)):
+                if spec[1] in _WINDOW_SHIFTS:
+                    # the argument's dtype and dictionary, nulls kept
+                    res[spec[0]] = Val(data, valid, f.cols[spec[2]].dict)
+                    continue
                 fill = _WINDOW_NULL_FILL.get(spec[1], 0.0)
                 if valid is not None and fill != 0.0:
                     data = torch.where(valid, data,

@@ -10,9 +10,17 @@ SMALL_ROWS = 2048
 TILE_ROWS = 2048
 CARRY_CHUNK = 1024  # tile carries per round of the carry scan
 
+# mirrors of src/gpu/window_rolling.hpp
+ROLL_TILE_ROWS = 1024  # sorted positions a workgroup of the rolling kernel owns
+ROLL_MAX_REACH = 512   # widest |lo|, |hi| the staged path takes
+ROLL_MAX_OFFSET = 2 ** 31 - 1
+_FN_SHIFT = 8          # lag and lead
+
 _RANKING = ("row_number", "rank", "dense_rank")
 _AGGREGATES = ("count", "sum", "min", "max", "avg")
+_SHIFTS = ("lag", "lead")
 _FUNCS = {fn: i for i, fn in enumerate(_RANKING + _AGGREGATES)}
+_CODES = dict(_FUNCS, lag=_FN_SHIFT, lead=_FN_SHIFT)
 _FRAMES = {"partition": 0, "rows": 1, "range": 2}
 _K_NONE, _K_BOOL, _K_SINT, _K_F32, _K_F64 = range(5)
 _VALUE_KINDS = {
@@ -43,6 +51,30 @@ class _Func:
     def nullable(self):
         return (self.fn not in _RANKING and self.fn != "count"
                 and self.valid is not None)
+
+
+class _RollFunc(_Func):
+    """One checked function of the rolling kernel: an aggregate over the
+    bounded frame [i + lo, i + hi], or lag / lead as the value `shift`
+    sorted positions away (lo = hi = shift)."""
+    __slots__ = ("lo", "hi", "shift")
+
+    def __init__(self, fn, values, valid, lo, hi, shift=0):
+        super().__init__(fn, values, valid, "rows")
+        self.lo, self.hi, self.shift = lo, hi, shift
+
+    def out_dtype(self):
+        if self.fn in _SHIFTS:
+            return self.values.dtype
+        return super().out_dtype()
+
+    def nullable(self):
+        if self.fn in _SHIFTS:
+            return True
+        if self.fn == "count":
+            return False
+        # a frame that leaves the current row out can be empty
+        return self.valid is not None or self.lo > 0 or self.hi < 0
 
 
 def _check_values(i, fn, values, valid, m, dev, anchor):
@@ -101,9 +133,14 @@ def _descriptor(f: _Func, m, data, ov):
             f.values = f.values.contiguous()
             stride = 1
         vptr = f.values.data_ptr()
-    return (_FUNCS[f.fn], _FRAMES[f.frame], kind, width, stride, vptr,
-            f.valid.data_ptr() if f.valid is not None else 0,
+    return (_CODES[f.fn], _FRAMES[f.frame], kind, width,
+            stride, vptr, f.valid.data_ptr() if f.valid is not None else 0,
             data.data_ptr(), ov.data_ptr() if ov is not None else 0)
+
+
+def _roll_descriptor(f: _RollFunc, m, data, ov):
+    """The tuple the rolling binding takes for f."""
+    return (_descriptor(f, m, data, ov), f.lo, f.hi, f.shift)
 
 
 def _work_buffer(nbytes, dev):

@@ -35,6 +35,7 @@ PYBIND11_MODULE(_gpu, m) {
   register_sort(m);
   register_sort_order(m);
   register_window(m);
+  register_window_rolling(m);
   register_seg_reduce(m);
   register_expr(m);
   register_rowconv(m);

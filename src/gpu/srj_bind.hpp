@@ -42,6 +42,7 @@ void register_parquet(py::module_& m);
 void register_sort(py::module_& m);
 void register_sort_order(py::module_& m);
 void register_window(py::module_& m);
+void register_window_rolling(py::module_& m);
 void register_seg_reduce(py::module_& m);
 void register_expr(py::module_& m);
 void register_lists(py::module_& m);
