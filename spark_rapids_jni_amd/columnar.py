@@ -265,29 +265,38 @@ class Table:
 
 
 # ---------------------------------------------------------------------------
-# ColDesc packing (flattened pre-order, matching src/gpu/srj_common.hpp)
+# ColDesc packing (flattened, siblings adjacent; src/gpu/srj_common.hpp)
 # ---------------------------------------------------------------------------
 
 def _flatten(cols: Sequence[Column]):
+    """Flatten column trees into one array. Returns (flat, top, child0):
+    top[i] is the index of cols[i], child0[j] the index of flat[j]'s first
+    child (0 for a leaf). The direct children of a node take consecutive
+    indices, child0 .. child0 + len(children) - 1, and their own subtrees
+    follow after that block, so a kernel reaches child k as
+    cols[child0 + k] whatever the siblings before it contain. For
+    STRUCT<STRUCT<int,float>, decimal> the array is [S, A, B, A.0, A.1]."""
     flat: List[Column] = []
+    child0: List[int] = []
     top: List[int] = []
 
-    def add(c: Column) -> int:
-        idx = len(flat)
-        flat.append(c)
-        return idx
-
-    def walk(c: Column) -> int:
-        idx = add(c)
-        child_idxs = [walk(ch) for ch in c.children]
-        # record first-child index; children are contiguous in pre-order only
-        # if each child subtree is flattened consecutively, which walk() does.
-        c._child0 = child_idxs[0] if child_idxs else 0
-        return idx
+    def place_children(idx: int) -> None:
+        kids = flat[idx].children
+        if not kids:
+            return
+        base = len(flat)
+        child0[idx] = base
+        flat.extend(kids)
+        child0.extend([0] * len(kids))
+        for k in range(len(kids)):
+            place_children(base + k)
 
     for c in cols:
-        top.append(walk(c))
-    return flat, top
+        top.append(len(flat))
+        flat.append(c)
+        child0.append(0)
+        place_children(top[-1])
+    return flat, top, child0
 
 
 # pinned staging for descriptor uploads. During hipGraph capture no pinned
@@ -329,7 +338,7 @@ def pack_descriptors(cols: Sequence[Column], device=None):
     Returns (desc_tensor, top_tensor, keepalive) where keepalive holds tensor
     references that must outlive the kernel launch.
     """
-    flat, top = _flatten(cols)
+    flat, top, child0 = _flatten(cols)
     device = device or flat[0].device
     raw = bytearray(COLDESC_BYTES * len(flat))
     for i, c in enumerate(flat):
@@ -338,7 +347,7 @@ def pack_descriptors(cols: Sequence[Column], device=None):
         offs_ptr = c.offsets.data_ptr() if c.offsets is not None else 0
         struct.pack_into(_COLDESC_FMT, raw, i * COLDESC_BYTES,
                          int(c.dtype), c.scale, data_ptr, valid_ptr, offs_ptr,
-                         len(c.children), getattr(c, "_child0", 0), c.size)
+                         len(c.children), child0[i], c.size)
     if (torch.cuda.is_available() and str(device).startswith("cuda")
             and torch.cuda.is_current_stream_capturing()):
         # hipGraph capture: pageable H2D is not capturable — stage through

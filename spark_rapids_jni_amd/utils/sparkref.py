@@ -291,15 +291,20 @@ def _hive_one(v, dt):
     if dt == DType.INT64:
         return _to_signed32(_to_signed64(v) ^ ((v & M64) >> 32))
     if dt == DType.TIMESTAMP_US:
-        sec, sub = divmod(v, 1000000)
-        nanos = sub * 1000
-        t = sec * 1000000000 + nanos
-        return _to_signed32(t ^ ((t & M64) >> 32))
+        # HiveHashFunction.hashTimestamp: Java / and % truncate toward zero
+        sec = abs(v) // 1000000 * (1 if v >= 0 else -1)
+        nanos = (v - sec * 1000000) * 1000
+        t = ((sec << 30) | nanos) & M64
+        return _to_signed32((t >> 32) ^ t)
+    # floatToIntBits / doubleToLongBits: canonical NaN, -0.0 keeps its sign
     if dt == DType.FLOAT32:
-        return _to_signed32(norm_float_bits(v))
+        if v != v:
+            return 0x7FC00000
+        return struct.unpack("<i", struct.pack("<f", v))[0]
     if dt == DType.FLOAT64:
-        b = norm_double_bits(v)
-        return _to_signed32(b ^ ((b & M64) >> 32))
+        b = (0x7FF8000000000000 if v != v
+             else struct.unpack("<Q", struct.pack("<d", v))[0])
+        return _to_signed32(b ^ (b >> 32))
     if dt == DType.STRING:
         h = 0
         for byte in (v.encode() if isinstance(v, str) else v):

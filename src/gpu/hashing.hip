@@ -24,9 +24,15 @@ __device__ uint32_t murmur3_col_row(const ColDesc* cols, const ColDesc& c,
                                     int64_t row, uint32_t seed, int depth);
 
 // struct/list members hash their elements in order with the running seed.
+// The direct children of a node sit at cols[child0 .. child0 + num_children)
+// (columnar._flatten lays them out that way, their subtrees after them).
+// ops/hashing.py refuses nesting deeper than MAX_STACK_DEPTH = 8 and dtypes a
+// hash does not define before any launch, so the depth guard below and the
+// `default:` of the switches only bound the recursion: nine frames of at most
+// 96 bytes per lane stay inside the runtime's 1 KiB default stack.
 __device__ uint32_t murmur3_children(const ColDesc* cols, const ColDesc& c,
                                      int64_t row, uint32_t seed, int depth) {
-  if (depth > 8) return seed;  // matches reference MAX_STACK_DEPTH-style cap
+  if (depth > 8) return seed;
   if (c.dtype == STRUCT) {
     uint32_t h = seed;
     for (int k = 0; k < c.num_children; ++k) {
@@ -213,27 +219,28 @@ __device__ int32_t hive_col_row(const ColDesc* cols, const ColDesc& c, int64_t r
       return (int32_t)(v ^ ((uint64_t)v >> 32));
     }
     case TIMESTAMP_US: {
-      // Hive TimestampWritableV2 hash: seconds ^ (seconds >>> 32) combined with nanos
+      // Spark HiveHashFunction.hashTimestamp: Java's truncating / and %, so
+      // the nanos of a negative timestamp are negative and their sign bits
+      // cover the shifted seconds.
       int64_t us = reinterpret_cast<const int64_t*>(c.data)[row];
       int64_t sec = us / 1000000;
-      int64_t sub = us % 1000000;
-      if (sub < 0) { sub += 1000000; sec -= 1; }
-      int64_t nanos = sub * 1000;
-      int64_t v = sec * 1000000000LL + nanos;
-      return (int32_t)(v ^ ((uint64_t)v >> 32));
+      int64_t nanos = (us % 1000000) * 1000;
+      int64_t v = (int64_t)((uint64_t)sec << 30) | nanos;
+      return (int32_t)(((uint64_t)v >> 32) ^ v);
     }
+    // floatToIntBits / doubleToLongBits: NaNs collapse to the canonical quiet
+    // NaN, every other bit pattern is kept, so -0.0 keeps its sign bit (the
+    // murmur3 and xxhash64 paths fold -0.0 into +0.0, hive does not).
     case FLOAT32: {
-      float f = reinterpret_cast<const float*>(c.data)[row];
-      int32_t b;
-      if (f != f) b = 0x7fc00000;
-      else { if (f == 0.0f) f = 0.0f; __builtin_memcpy(&b, &f, 4); }
+      int32_t b = reinterpret_cast<const int32_t*>(c.data)[row];
+      if ((b & 0x7f800000) == 0x7f800000 && (b & 0x007fffff)) b = 0x7fc00000;
       return b;
     }
     case FLOAT64: {
-      double d = reinterpret_cast<const double*>(c.data)[row];
-      int64_t b;
-      if (d != d) b = 0x7ff8000000000000LL;
-      else { if (d == 0.0) d = 0.0; __builtin_memcpy(&b, &d, 8); }
+      int64_t b = reinterpret_cast<const int64_t*>(c.data)[row];
+      if ((b & 0x7ff0000000000000LL) == 0x7ff0000000000000LL &&
+          (b & 0x000fffffffffffffLL))
+        b = 0x7ff8000000000000LL;
       return (int32_t)(b ^ ((uint64_t)b >> 32));
     }
     case STRING: {

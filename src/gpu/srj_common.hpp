@@ -66,7 +66,8 @@ __host__ __device__ inline int dtype_size(int32_t t) {
 
 // ---------------------------------------------------------------------------
 // Column descriptor passed across the C ABI. Flat (nested columns are passed
-// as a flattened pre-order array; `child0` indexes into that array).
+// as one flattened array in which the direct children of a node are adjacent:
+// child k of a node is entry `child0 + k`, the children's subtrees follow).
 // ---------------------------------------------------------------------------
 struct ColDesc {
   int32_t dtype;

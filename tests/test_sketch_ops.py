@@ -22,6 +22,11 @@ def test_sha2(bits, fn):
             "x" * 55, "y" * 56, "z" * 63, "w" * 64, "v" * 65,
             "long " * 100,
             "".join(chr(random.randint(32, 126)) for _ in range(200))]
+    # SHA-384/512 pad to 128-byte blocks with a 16-byte length: 111 is the
+    # last length whose padding fits the block, 112 the first that spills
+    vals += [chr(97 + n % 26) * n for n in (111, 112, 119, 120, 127, 128, 129)]
+    # multi-byte UTF-8: 2-, 3- and 4-byte sequences, hashed as bytes
+    vals += ["naïve Ünicode – 雪 ❄ 𝄞", "é" * 56, "雪" * 37 + "x"]
     col = Column.from_pylist(vals, DType.STRING, "cuda")
     got = sha2(col, bits).to_pylist()
     for v, gs in zip(vals, got):
