@@ -546,6 +546,53 @@ def join_dense_bench(nb, npr, iters, dev, g):
         tables.clear()
 
 
+def join_ordered_bench(nb, npr, iters, dev, g):
+    """Ordered (no table) against dense (direct-address table), both forced,
+    on the same sorted int64 keys; build and probe timed separately and
+    alternating. The ordered build is the key scan and its read-back; the
+    dense build is the min/max scan with its read-back, the zero fill, the
+    build kernel and the read-back of its duplicate flag."""
+    from spark_rapids_jni_amd.columnar import Column, DType
+    from spark_rapids_jni_amd.ops.join import HashJoinTable
+    bcol = Column(DType.INT64, nb,
+                  torch.arange(nb, dtype=torch.int64, device=dev) + 100)
+    pcol = Column(DType.INT64, npr, torch.randint(
+        0, 2 * nb, (npr,), dtype=torch.int64, device=dev, generator=g))
+    kw = {"ordered": {"ordered": True}, "dense": {"dense": True}}
+    tables = {}
+
+    def build(path):
+        def run():
+            tables[path] = None  # one table resident at a time
+            tables[path] = HashJoinTable.build(bcol, **kw[path])
+        return run
+
+    def probe(path):
+        return lambda: tables[path].inner_join(pcol, out_hint=npr)
+
+    for phase, fn in (("build", build), ("probe", probe)):
+        rows = nb if phase == "build" else npr
+        if phase == "probe":
+            for path in kw:
+                tables[path] = HashJoinTable.build(bcol, **kw[path])
+                assert tables[path].layout == path
+            a, b = probe("ordered")(), probe("dense")()
+            assert a[0].numel() == b[0].numel()
+            assert torch.equal((a[0] ^ a[1]).sum(), (b[0] ^ b[1]).sum())
+            del a, b
+        ordd, den = ab_time(fn("ordered"), fn("dense"), iters, repeats=3)
+        for path, xs in (("ordered", ordd), ("dense", den)):
+            xs = sorted(xs)
+            print(json.dumps({
+                "bench": f"join_ordered_{phase}", "path": path,
+                "build_rows": nb, "probe_rows": npr,
+                "ms": round(xs[1] * 1e3, 4),
+                "ms_min": round(xs[0] * 1e3, 4),
+                "ms_max": round(xs[2] * 1e3, 4),
+                "rows_per_sec": round(rows / xs[1], 1)}), flush=True)
+    tables.clear()
+
+
 def join_modes_bench(nb, npr, iters, dev, g):
     """Semi, anti and left outer joins as emit modes of the fast-path probe
     (semi_select, left_outer_join) against the parent's expressions, copied
@@ -644,7 +691,8 @@ def main():
     ap.add_argument("--rows", type=int, default=2**24)
     ap.add_argument("--iters", type=int, default=5)
     ap.add_argument("--only", choices=["sort_order", "join_narrow",
-                                      "join_dense", "join_modes", "window",
+                                      "join_dense", "join_ordered",
+                                      "join_modes", "window",
                                       "window_rolling", "expr",
                                       "groupby_sorted"],
                     default=None,
@@ -695,6 +743,13 @@ def main():
         # beyond the Infinity Cache, then cache resident
         for nb, npr in ((2**26, 2**26), (2**20, 2**24)):
             join_dense_bench(nb, npr, args.iters, "cuda", g)
+        return
+    if args.only == "join_ordered":
+        g = torch.Generator(device="cuda")
+        g.manual_seed(7)
+        # beyond the Infinity Cache, then cache resident
+        for nb, npr in ((2**26, 2**26), (2**20, 2**24)):
+            join_ordered_bench(nb, npr, args.iters, "cuda", g)
         return
     if args.only == "join_modes":
         g = torch.Generator(device="cuda")

@@ -93,10 +93,28 @@ def _fits_narrow(lo: int, hi: int) -> bool:
 
 
 def _key_range(data: torch.Tensor) -> Tuple[int, int]:
-    """(min, max) of a key tensor as Python ints: one pass, one read-back."""
+    """(min, max) of a key tensor as Python ints: one pass, one read-back.
+    Only the forced dense build still scans with torch: its native calls are
+    exactly one build and the probes (tests/test_join_dense.py pins them)."""
     lo, hi = torch.aminmax(data)
     lo, hi = torch.stack([lo, hi]).cpu().tolist()
     return int(lo), int(hi)
+
+
+def _scan_keys(data: torch.Tensor, key_i32: int,
+               valid: Optional[torch.Tensor], n: int) -> Tuple[int, int, bool]:
+    """(min, max, ordered) of the first n >= 1 keys of an int32 / int64
+    tensor: one pass of join_scan_keys (src/gpu/join_fast.hip), one read-back.
+    `ordered`: row i holds key min + i for every i and, where a mask is
+    given, no row is null. The kernel's flag says key[i] - key[0] == i in
+    unsigned arithmetic; max - min == n - 1 rejects the one sequence that
+    passes it without being ascending, one that wraps past INT64_MAX."""
+    out = torch.empty(3, dtype=torch.int64, device=data.device)
+    _native.gpu().join_scan_keys(
+        data.data_ptr(), key_i32, valid.data_ptr() if valid is not None else 0,
+        n, out.data_ptr(), _native.current_stream())
+    lo, hi, flag = out.cpu().tolist()
+    return lo, hi, bool(flag) and hi - lo == n - 1
 
 
 def _narrow_keys(c: Column) -> Tuple[torch.Tensor, int]:
@@ -170,19 +188,24 @@ class HashJoinTable:
     """Build-side hash table reusable across probes (reference: the build/probe
     split of hash_inner_join).
 
-    Four layouts (`layout`): "generic", a (fingerprint32|row+1) single-word
+    Five layouts (`layout`): "generic", a (fingerprint32|row+1) single-word
     table for any key schema; "wide", the specialized 16-byte {key,row} table
     for single integer keys that need 64 bits; "narrow", one 8-byte word
     (key - kmin | row+1 | chain) per slot for keys whose range fits 32 bits —
-    INT32/DATE32 columns, packed tuples, int64 surrogate keys; and "dense",
+    INT32/DATE32 columns, packed tuples, int64 surrogate keys; "dense",
     a direct-address table of one 4-byte word (row+1) per key of
     [kmin, kmin + capacity) with no hashing at all, for a single integer key
     column that is duplicate-free and whose range is at most
-    DENSE_MAX_SLOTS_PER_ROW slots per row. Wide, narrow and dense are the
-    software-pipelined fast path (`i64_fast`), see src/gpu/join_fast.hip and
-    its one probe kernel, src/gpu/join_probe.hpp. `capacity` is the slot
-    count in every layout; it is a power of two except for dense, where it is
-    the key range.
+    DENSE_MAX_SLOTS_PER_ROW slots per row; and "ordered", no table at all
+    (`slots` is None), for a single integer key column without nulls whose
+    row i holds key kmin + i: a dimension table written in surrogate-key
+    order, or a contiguous range of one. The word the dense table would hold
+    for a key is then key - kmin + 1, and the probe computes it. Wide,
+    narrow, dense and ordered are the software-pipelined fast path
+    (`i64_fast`), see src/gpu/join_fast.hip and its one probe kernel,
+    src/gpu/join_probe.hpp. `capacity` is the slot count in every layout; it
+    is a power of two except for dense, where it is the key range, and
+    ordered, where it is the build row count.
 
     Probes: `inner_join`, `left_outer_join`, `full_outer_join` give gather
     maps; `semi_select` gives the ascending probe rows of a semi or anti
@@ -209,7 +232,8 @@ class HashJoinTable:
     def build(keys: Union[Column, Table, Sequence[Column]],
               force_generic: bool = False,
               narrow: Optional[bool] = None,
-              dense: Optional[bool] = None) -> "HashJoinTable":
+              dense: Optional[bool] = None,
+              ordered: Optional[bool] = None) -> "HashJoinTable":
         """narrow: True forces the 8-byte-slot table (raises if the key range
         does not fit 32 bits), False forbids it (wide), None decides:
         4-byte-or-less key columns and packed tuples of width product <= 2^32
@@ -223,7 +247,18 @@ class HashJoinTable:
         range builds the direct table and reads back its duplicate flag (one
         more read-back; the probe cannot start before the build ends); if a
         key repeats the table is dropped and the narrow build goes ahead with
-        the range already known."""
+        the range already known. dense=True gives "dense" whatever the key
+        order.
+
+        ordered: True forces the table-free layout for a single integer key
+        column of any width and row count, zero included (scans the keys;
+        raises if a row is null or row i does not hold key[0] + i, or if
+        another layout is forced with it), False forbids it. None applies
+        where dense=None does: the scan that finds the range of an int64
+        column finds the order in the same pass, and an ordered column
+        returns right after the scan's read-back, with no slots, no zero
+        fill, no build kernel and no second read-back. The scan runs again
+        on every build; nothing is cached between calls."""
         cols = _keys(keys)
         n = cols[0].size
         assert n < 2**31, "build side capped at 2^31-1 rows (chunk the build)"
@@ -261,6 +296,23 @@ class HashJoinTable:
             if bad:
                 return None
             return HashJoinTable(cols, slots, span, None, True, "dense", lo)
+
+        def ordered_table(lo):
+            return HashJoinTable(cols, None, n, None, True, "ordered", lo)
+
+        if ordered:
+            if (force_generic or narrow is not None or dense
+                    or not _is_i64_fast(cols)):
+                raise ValueError("ordered=True needs a single integer key "
+                                 "column and no other layout forced")
+            if n == 0:
+                return ordered_table(0)
+            data, key_i32 = _narrow_keys(cols[0])
+            lo, hi, is_ord = _scan_keys(data, key_i32, cols[0].validity, n)
+            if not is_ord:
+                raise ValueError("ordered=True: a build row is null or row i "
+                                 "does not hold key[0] + i")
+            return ordered_table(lo)
 
         if dense:
             if force_generic or narrow is not None or not _is_i64_fast(cols):
@@ -308,9 +360,15 @@ class HashJoinTable:
                     return build_narrow(data, key_i32, c0.validity, _I32_KMIN,
                                         data)
                 if narrow or n >= NARROW_SCAN_MIN_ROWS:
-                    lo, hi = _key_range(c0.data) if n else (0, 0)
-                    if (narrow is None and dense is None
-                            and _is_dense(lo, hi, n)):
+                    auto = narrow is None and dense is None
+                    try_ord = auto and ordered is None
+                    lo, hi, is_ord = (
+                        _scan_keys(c0.data, 0,
+                                   c0.validity if try_ord else None, n)
+                        if n else (0, 0, False))
+                    if try_ord and is_ord:
+                        return ordered_table(lo)
+                    if auto and _is_dense(lo, hi, n):
                         tbl = build_dense(c0.data, 0, c0.validity, lo, hi)
                         if tbl is not None:
                             return tbl
@@ -357,7 +415,7 @@ class HashJoinTable:
                           null_count=None)
         if not _is_i64_fast(pcols):
             return None
-        if self.layout in ("narrow", "dense"):
+        if self.layout in ("narrow", "dense", "ordered"):
             return pcols[0]  # read in place, whatever its integer width
         return _as_i64_keys(pcols[0])
 
@@ -365,7 +423,13 @@ class HashJoinTable:
                     out_capacity, matched, fill, stream):
         g = _native.gpu()
         pvalid = p.validity.data_ptr() if p.validity is not None else 0
-        if self.layout == "dense":
+        if self.layout == "ordered":
+            data, key_i32 = _narrow_keys(p)
+            g.join_probe_ord(data.data_ptr(), key_i32, pvalid, p.size,
+                             self.capacity, self.kmin, counter.data_ptr(),
+                             out_build, out_probe, out_capacity, matched,
+                             fill, stream)
+        elif self.layout == "dense":
             data, key_i32 = _narrow_keys(p)
             g.join_probe_d32(data.data_ptr(), key_i32, pvalid, p.size,
                              self.slots.data_ptr(), self.capacity, self.kmin,
@@ -395,6 +459,12 @@ class HashJoinTable:
                                   matched, fill, mode, probe_hit, anti, stream)
             return
         data, key_i32 = _narrow_keys(p)
+        if self.layout == "ordered":
+            g.join_probe_mode_ord(data.data_ptr(), key_i32, pvalid, p.size,
+                                  self.capacity, self.kmin, counter,
+                                  out_build, out_probe, out_capacity, matched,
+                                  fill, mode, probe_hit, anti, stream)
+            return
         fn = (g.join_probe_mode_d32 if self.layout == "dense"
               else g.join_probe_mode_n32)
         fn(data.data_ptr(), key_i32, pvalid, p.size, self.slots.data_ptr(),
@@ -523,8 +593,13 @@ class HashJoinTable:
         fast = p is not None
         if not fast:
             bdesc, btop, pdesc, ptop, keep = self._descs(pcols)
-        # Measured and rejected, twice: grouping the probe rows by table
-        # window before the probe. By hash prefix into a 64 GiB hashed table
+        # Where the probe's time goes is the random fetch of a table word per
+        # row: ~25 ms per 1B-row chunk against the dense table, the rate of
+        # 64 B requests past an XCD's L2 (~3.2 TB/s, the same from the
+        # Infinity Cache as from HBM). The "ordered" layout has no such fetch
+        # and streams (docs/PERF.md, "ordered"). For every layout that has a
+        # table, measured and rejected, twice: grouping the probe rows by
+        # table window before the probe. By hash prefix into a 64 GiB hashed table
         # (part_hist/part_scatter + idxmap probe) each 64 B line is touched
         # only ~1.4x per 1B chunk and the scatter cost 29 ms per chunk
         # (profiles/r01_bench_join_22.1B.json). By key range into the 3.7 GiB

@@ -47,6 +47,15 @@ void srj_join_probe_d32(const void*, int32_t, const uint8_t*, int64_t,
                         const void*, int64_t, long long, uint64_t*, int32_t*,
                         int64_t*, int64_t, uint8_t*, int32_t, hipStream_t);
 int32_t srj_join_probe_tile(int32_t);
+void srj_join_scan_keys(const void*, int32_t, const uint8_t*, int64_t,
+                        long long*, hipStream_t);
+void srj_join_probe_ord(const void*, int32_t, const uint8_t*, int64_t, int64_t,
+                        long long, uint64_t*, int32_t*, int64_t*, int64_t,
+                        uint8_t*, int32_t, hipStream_t);
+void srj_join_probe_mode_ord(const void*, int32_t, const uint8_t*, int64_t,
+                             int64_t, long long, uint64_t*, int32_t*,
+                             int64_t*, int64_t, uint8_t*, int32_t, int32_t,
+                             uint8_t*, int32_t, hipStream_t);
 void srj_join_probe_mode_i64(const long long*, const uint8_t*, int64_t,
                              const void*, int64_t, uint64_t*, int32_t*,
                              int64_t*, int64_t, uint8_t*, int32_t, int32_t,
@@ -74,7 +83,8 @@ void register_hashtable(py::module_& m) {
   m.attr("JOIN_PROBE_TILE") =
       py::dict(py::arg("wide") = srj_join_probe_tile(0),
                py::arg("narrow") = srj_join_probe_tile(1),
-               py::arg("dense") = srj_join_probe_tile(2));
+               py::arg("dense") = srj_join_probe_tile(2),
+               py::arg("ordered") = srj_join_probe_tile(3));
   m.def("join_build",
         [](uintptr_t cols, uintptr_t top, int32_t ntop, int64_t nrows,
            uintptr_t slots, int64_t capacity, uintptr_t stream) {
@@ -271,6 +281,44 @@ void register_hashtable(py::module_& m) {
               as_ptr<uint8_t>(build_matched), fill, mode,
               as_ptr<uint8_t>(probe_hit), anti, as_stream(stream));
           check_hip("join_probe_mode_d32");
+        });
+  m.def("join_scan_keys",
+        [](uintptr_t keys, int32_t key_i32, uintptr_t valid, int64_t n,
+           uintptr_t out, uintptr_t stream) {
+          if (n < 1) throw std::invalid_argument("join_scan_keys needs n >= 1");
+          srj_join_scan_keys(as_ptr<void>(keys), key_i32,
+                             as_ptr<uint8_t>(valid), n, as_ptr<long long>(out),
+                             as_stream(stream));
+          check_hip("join_scan_keys");
+        });
+  m.def("join_probe_ord",
+        [](uintptr_t probe, int32_t key_i32, uintptr_t pvalid, int64_t nprobe,
+           int64_t range, int64_t kmin, uintptr_t counter,
+           uintptr_t out_build, uintptr_t out_probe, int64_t out_capacity,
+           uintptr_t build_matched, int32_t fill, uintptr_t stream) {
+          srj_join_probe_ord(as_ptr<void>(probe), key_i32,
+                             as_ptr<uint8_t>(pvalid), nprobe, range,
+                             (long long)kmin, as_ptr<uint64_t>(counter),
+                             as_ptr<int32_t>(out_build),
+                             as_ptr<int64_t>(out_probe), out_capacity,
+                             as_ptr<uint8_t>(build_matched), fill,
+                             as_stream(stream));
+          check_hip("join_probe_ord");
+        });
+  m.def("join_probe_mode_ord",
+        [](uintptr_t probe, int32_t key_i32, uintptr_t pvalid, int64_t nprobe,
+           int64_t range, int64_t kmin, uintptr_t counter,
+           uintptr_t out_build, uintptr_t out_probe, int64_t out_capacity,
+           uintptr_t build_matched, int32_t fill, int32_t mode,
+           uintptr_t probe_hit, int32_t anti, uintptr_t stream) {
+          check_probe_mode(mode, probe_hit);
+          srj_join_probe_mode_ord(
+              as_ptr<void>(probe), key_i32, as_ptr<uint8_t>(pvalid), nprobe,
+              range, (long long)kmin, as_ptr<uint64_t>(counter),
+              as_ptr<int32_t>(out_build), as_ptr<int64_t>(out_probe),
+              out_capacity, as_ptr<uint8_t>(build_matched), fill, mode,
+              as_ptr<uint8_t>(probe_hit), anti, as_stream(stream));
+          check_hip("join_probe_mode_ord");
         });
   m.def("part_hist",
         [](uintptr_t keys, int64_t n, int32_t pbits, uintptr_t hist,

@@ -16,6 +16,9 @@
 //   narrow  8-byte key-kmin | row+1 | chain words, key range within 32 bits
 //   dense   4-byte row+1 words addressed by key-kmin, no hashing, for a
 //           duplicate-free key column of a dense range
+//   ordered no table at all: build row i holds key kmin + i, so the word the
+//           dense table would hold at key-kmin is key-kmin+1. One scan of the
+//           build keys (join_scan_keys) finds the range and this order.
 #include "i64_slots.hpp"
 #include "join_probe.hpp"
 
@@ -289,6 +292,136 @@ struct DenseLayout {
   __device__ static uint32_t row1(Word w) { return w; }
 };
 
+// ---------------------------------------------------------------------------
+// ordered build keys: key[i] = kmin + i for every row, all rows valid. The
+// dense table of such a column would hold slots[o] = o + 1, so the probe
+// computes the word from the key it has already loaded and touches no table:
+// it streams keys in and pairs out. The offset rules are the dense table's.
+// ---------------------------------------------------------------------------
+struct OrderedLayout {
+  struct Tag {};
+  using Word = uint32_t;
+  using Index = uint32_t;  // the word itself; load() is the identity
+  static constexpr bool CHAINED = false;
+  static constexpr bool WG_APPEND = true;
+  static constexpr bool NT_OUT = true;
+  uint64_t range;  // build rows, below 2^31
+  long long kmin;
+
+  __device__ Index index(long long key, Tag&, bool& live) const {
+    uint64_t o = (uint64_t)key - (uint64_t)kmin;
+    live = o < range;
+    return live ? (uint32_t)o + 1u : 0u;
+  }
+  __device__ Word load(Index i) const { return i; }
+  __device__ static bool empty(Word w) { return w == 0; }
+  __device__ static bool match(Word, Tag) { return true; }
+  __device__ static uint32_t row1(Word w) { return w; }
+};
+
+// One pass over a single integer key column: signed min, signed max, and
+// whether the column is ordered, i.e. every row i is valid and
+// (uint64)key[i] - (uint64)key[0] == i (an int key is sign-extended first).
+// out = {min, max, ordered}, initialised to {INT64_MAX, INT64_MIN, 1} by
+// join_scan_init_kernel on the same stream; each workgroup reduces per wave,
+// then through LDS, and finishes with one atomic min, one atomic max and, if
+// it saw a violation, one atomic and. No workgroup waits on another.
+// VEC: 16-byte loads (keys 16-byte aligned); rows past the last whole vector
+// are taken one per thread by the first threads of the grid. A vector index
+// past the end is clamped to the thread's first one: re-reducing a row
+// changes nothing, so the SCAN_UNROLL loads of an iteration issue together
+// with no branch between them. Validity is read only when a mask is given,
+// one byte per vector (a vector never straddles a byte), and only bits of
+// rows below n are looked at. Min and max cover null rows too, as the
+// range scan they replace did.
+// ---------------------------------------------------------------------------
+constexpr int SCAN_UNROLL = 4;
+
+__global__ void join_scan_init_kernel(long long* __restrict__ out) {
+  out[0] = INT64_MAX;
+  out[1] = INT64_MIN;
+  out[2] = 1;
+}
+
+template <typename K, bool VEC>
+__global__ void __launch_bounds__(DEFAULT_BLOCK)
+join_scan_keys_kernel(const K* __restrict__ keys,
+                      const uint8_t* __restrict__ valid, int64_t n,
+                      long long* __restrict__ out) {
+  constexpr int N = VEC ? 16 / (int)sizeof(K) : 1;
+  struct alignas(sizeof(K) * N) Vec {
+    K e[N];
+  };
+  constexpr int NW = DEFAULT_BLOCK / WAVE;
+  __shared__ long long slo[NW], shi[NW];
+  __shared__ uint32_t sbad[NW];
+  const Vec* __restrict__ vk = reinterpret_cast<const Vec*>(keys);
+  const int64_t nvec = n / N;
+  const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t nthreads = (int64_t)gridDim.x * blockDim.x;
+  const uint64_t k0 = (uint64_t)(long long)keys[0];  // n >= 1
+  long long lo = INT64_MAX, hi = INT64_MIN;
+  bool bad = false;
+  auto take = [&](K key, int64_t row, uint32_t vbyte) {
+    long long k = (long long)key;
+    lo = k < lo ? k : lo;
+    hi = k > hi ? k : hi;
+    bad |= (uint64_t)k - k0 != (uint64_t)row;
+    bad |= !((vbyte >> (row & 7)) & 1u);
+  };
+  for (int64_t v0 = tid; v0 < nvec; v0 += nthreads * SCAN_UNROLL) {
+    Vec x[SCAN_UNROLL];
+    uint32_t vb[SCAN_UNROLL];
+#pragma unroll
+    for (int u = 0; u < SCAN_UNROLL; ++u) {
+      int64_t v = v0 + u * nthreads;
+      v = v < nvec ? v : v0;
+      x[u] = vk[v];
+      vb[u] = valid ? (uint32_t)valid[(v * N) >> 3] : 0xffu;
+    }
+#pragma unroll
+    for (int u = 0; u < SCAN_UNROLL; ++u) {
+      int64_t v = v0 + u * nthreads;
+      v = v < nvec ? v : v0;
+#pragma unroll
+      for (int j = 0; j < N; ++j) take(x[u].e[j], v * N + j, vb[u]);
+    }
+  }
+  {
+    int64_t row = nvec * N + tid;
+    if (row < n)
+      take(keys[row], row, valid ? (uint32_t)valid[row >> 3] : 0xffu);
+  }
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int wave = threadIdx.x / WAVE;
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    long long l = __shfl_down(lo, off, WAVE);
+    long long h = __shfl_down(hi, off, WAVE);
+    lo = l < lo ? l : lo;
+    hi = h > hi ? h : hi;
+  }
+  const bool wbad = __ballot(bad) != 0;
+  if (lane == 0) {
+    slo[wave] = lo;
+    shi[wave] = hi;
+    sbad[wave] = wbad;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    uint32_t b = 0;
+#pragma unroll
+    for (int w = 0; w < NW; ++w) {
+      lo = slo[w] < lo ? slo[w] : lo;
+      hi = shi[w] > hi ? shi[w] : hi;
+      b |= sbad[w];
+    }
+    atomicMin(&out[0], lo);
+    atomicMax(&out[1], hi);
+    if (b) atomicAnd(reinterpret_cast<unsigned long long*>(&out[2]), 0ull);
+  }
+}
+
 // Dense probe geometry, chosen by measurement (docs/PERF.md): 8 rows per lane
 // keeps 8 waves per SIMD, and a 1024-thread workgroup reserves output space
 // once per 8192 rows. With the workgroup append, 16 rows per lane no longer
@@ -360,15 +493,57 @@ static void probe_dense(const void* probe, int32_t key_i32,
                                                     nprobe, l, o, stream);
 }
 
+// Ordered probe geometry, chosen by measurement (docs/PERF.md, "ordered"):
+// with no random load the kernel streams, and what is left to amortise is the
+// reservation, two barriers and one atomic per tile. 16 rows per lane in a
+// 1024-thread workgroup reserve once per 16384 rows; with nontemporal pair
+// stores that is 3.30 ms per 1B rows against 3.55 at 8 rows per lane with
+// plain stores, and 6.2 at 256 threads x 8 rows.
+constexpr int ORD_PPIPE = 16;
+constexpr int ORD_BLOCK = 1024;
+
+static void probe_ordered(const void* probe, int32_t key_i32,
+                          const uint8_t* pvalid, int64_t nprobe, int64_t range,
+                          long long kmin, const ProbeOut& o,
+                          hipStream_t stream) {
+  OrderedLayout l{(uint64_t)range, kmin};
+  probe_keys<OrderedLayout, ORD_PPIPE, ORD_BLOCK>(probe, key_i32, pvalid,
+                                                  nprobe, l, o, stream);
+}
+
 }  // namespace srj
 
 using namespace srj;
 
 extern "C" {
 
-// probe rows per workgroup and iteration: layout 0 wide, 1 narrow, 2 dense
+// probe rows per workgroup and iteration: layout 0 wide, 1 narrow, 2 dense,
+// 3 ordered
 int32_t srj_join_probe_tile(int32_t layout) {
+  if (layout == 3) return ORD_BLOCK * ORD_PPIPE;
   return layout == 2 ? DENSE_BLOCK * DENSE_PPIPE : DEFAULT_BLOCK * PIPE;
+}
+
+// out: three int64 words {min, max, ordered} (see the kernel); n >= 1.
+void srj_join_scan_keys(const void* keys, int32_t key_i32,
+                        const uint8_t* valid, int64_t n, long long* out,
+                        hipStream_t stream) {
+  join_scan_init_kernel<<<1, 1, 0, stream>>>(out);
+  const bool vec = (reinterpret_cast<uintptr_t>(keys) & 15u) == 0;
+  const int per = vec ? (key_i32 ? 4 : 2) : 1;
+  int64_t g = grid_1d((n / per + SCAN_UNROLL - 1) / SCAN_UNROLL);
+  auto launch = [&](auto* k, auto kernel) {
+    kernel<<<g, DEFAULT_BLOCK, 0, stream>>>(k, valid, n, out);
+  };
+  if (key_i32) {
+    auto* k = reinterpret_cast<const int*>(keys);
+    if (vec) launch(k, join_scan_keys_kernel<int, true>);
+    else launch(k, join_scan_keys_kernel<int, false>);
+  } else {
+    auto* k = reinterpret_cast<const long long*>(keys);
+    if (vec) launch(k, join_scan_keys_kernel<long long, true>);
+    else launch(k, join_scan_keys_kernel<long long, false>);
+  }
 }
 
 void srj_join_build_i64(const long long* keys, const uint8_t* valid, int64_t nrows,
@@ -492,6 +667,32 @@ void srj_join_probe_mode_d32(const void* probe, int32_t key_i32,
               {counter, out_build, out_probe, out_capacity, build_matched,
                fill, nullptr, (ProbeEmit)mode, probe_hit, anti},
               stream);
+}
+
+// the _d32 entry points without a table: build rows are [kmin, kmin + range)
+void srj_join_probe_ord(const void* probe, int32_t key_i32,
+                        const uint8_t* pvalid, int64_t nprobe, int64_t range,
+                        long long kmin, uint64_t* counter, int32_t* out_build,
+                        int64_t* out_probe, int64_t out_capacity,
+                        uint8_t* build_matched, int32_t fill,
+                        hipStream_t stream) {
+  probe_ordered(probe, key_i32, pvalid, nprobe, range, kmin,
+                {counter, out_build, out_probe, out_capacity, build_matched,
+                 fill, nullptr, ProbeEmit::INNER, nullptr, 0},
+                stream);
+}
+
+void srj_join_probe_mode_ord(const void* probe, int32_t key_i32,
+                             const uint8_t* pvalid, int64_t nprobe,
+                             int64_t range, long long kmin, uint64_t* counter,
+                             int32_t* out_build, int64_t* out_probe,
+                             int64_t out_capacity, uint8_t* build_matched,
+                             int32_t fill, int32_t mode, uint8_t* probe_hit,
+                             int32_t anti, hipStream_t stream) {
+  probe_ordered(probe, key_i32, pvalid, nprobe, range, kmin,
+                {counter, out_build, out_probe, out_capacity, build_matched,
+                 fill, nullptr, (ProbeEmit)mode, probe_hit, anti},
+                stream);
 }
 
 }  // extern "C"

@@ -69,6 +69,7 @@
 //   CHAINED       false: at most one match per key, no chain walk, no idxmap,
 //                 interleaved rows, and next, reindex and chain are not needed
 //   WG_APPEND     one reservation per workgroup and tile (see above)
+//   NT_OUT        optional; true: out_build and out_probe stores are nontemporal
 #pragma once
 #include <type_traits>
 
@@ -86,6 +87,13 @@ __device__ inline uint64_t bits_to_bytes(uint32_t m) {
   uint32_t hi = (m & 1u) | (m & 2u) << 7 | (m & 4u) << 14 | (m & 8u) << 21;
   return (uint64_t)hi << 32 | lo;
 }
+
+// A layout that declares NT_OUT = true has its pairs stored nontemporal: they
+// are written once and never read by the kernel.
+template <typename L, typename = void>
+struct nt_out : std::false_type {};
+template <typename L>
+struct nt_out<L, std::enable_if_t<L::NT_OUT>> : std::true_type {};
 
 template <typename L, typename K, bool FILL, bool HAS_VALID, int PPIPE,
           int BLOCK, ProbeEmit EMIT = ProbeEmit::INNER>
@@ -334,8 +342,13 @@ join_probe_kernel_t(const K* __restrict__ probe,
                 ((below[b / 4] >> (8 * (b % 4))) & 0xffu);
         auto emit = [&](uint32_t r1) {
           if (pos < out_capacity) {
-            out_build[pos] = (int32_t)(r1 - 1);
-            out_probe[pos] = prow;
+            if constexpr (nt_out<L>::value) {
+              __builtin_nontemporal_store((int32_t)(r1 - 1), &out_build[pos]);
+              __builtin_nontemporal_store(prow, &out_probe[pos]);
+            } else {
+              out_build[pos] = (int32_t)(r1 - 1);
+              out_probe[pos] = prow;
+            }
           }
           // OUTER: r1 == 0 is an unmatched probe row, build index -1
           if (build_matched && (!OUTER || r1)) build_matched[r1 - 1] = 1;
